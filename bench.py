@@ -16,7 +16,13 @@ measured beside the headline (`per_gpu_batch`), and the reference's decode ENTRY
 (`generate_batch`).  Inputs and state are resident in HBM when the timed region starts.  Synthetic
 data, seeded random-init weights from the reference initialisers.
 
-Prints ONE JSON line (rank 0) with the driver contract plus
+Prints ONE JSON line (rank 0) with the driver contract (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...) and `step_roofline`.  A plain run does only that: set up, warm up, time the steps, print.
+`--dump-outputs DIR` then also writes what the timed loop computed in its last step (tokens, attention weights; with
+`--train` the loss and a seeded sample of the updated parameters) as DIR/<name>.npy; the recurrent state is reset before
+the timed loop is armed, so the same arguments give the same outputs.
+`--full` adds the secondary measurements below, each a run of its own after the timed region:
+  sustained     the same loop over >= 0.25 s right after the timed region
   roofline      the dominant kernel of the step -- K1w + K5 (lina::gla_decode_window_kernel), the windowed recurrent-state
                 update: its bytes per launch / its launch duration measured IN SITU (the captured step graph
                 with and without its 13 update launches, HIP events around the replays), the back-to-back figure and the
@@ -26,7 +32,7 @@ Prints ONE JSON line (rank 0) with the driver contract plus
   other_head_shapes / decode_f32   the same engine at H=8, H=16, expand_v=2 and in fp32
   cpu_baseline  the CPU oracle (pure-PyTorch recurrent port of the reference path) on a bounded sample, host CPU named
 `--gpus N` without a launcher starts N ranks under torch.distributed.run; `--train` measures config 5 (DDP train step).
-The timed region is max(--steps, 0.25 s of steps); "steps" reports what was timed.
+The timed region is exactly --steps steps (more only with --min-timed-s); "steps" reports what was timed.
 """
 from __future__ import annotations
 
@@ -572,6 +578,31 @@ def timed_steps(run_step, k_req, dist, dev, est_steps=None, batched=False):
     return elapsed, k
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each tensor of ``arrays`` as out_dir/<name>.npy in float32 (at most DUMP_LIMIT_BYTES in all)."""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log("bench.py: wrote", ", ".join(f"{n}.npy {list(a.shape)}" for n, a in host.items()), "to", out_dir)
+
+
+def last_step_outputs(engines):
+    """What the decode loop handed its caller for the LAST step it ran: the token picked for every row and quantizer
+    (tokens [Q, B]) and the cross-attention weights of the step (attention [B, 2, T_txt]), rows in batch order."""
+    torch.cuda.synchronize()
+    toks = torch.cat([e._loop.tok_log[e._n_done - 1] for e in engines], dim=1)
+    atts = torch.cat([e._loop.att_log[:, :, e._n_done - 1] for e in engines], dim=0)
+    return {"tokens": toks, "attention": atts}
+
+
 def bench_train(args):
     """--train: config 5 -- the L169 training step (teacher-forced forward, CE, backward through K2b/K3b/K5b, AdamW;
     bf16 autocast, fp32 master weights) with b = 8 sequences of 4096 tokens PER GPU, data parallel over RCCL
@@ -592,14 +623,25 @@ def bench_train(args):
     for _ in range(max(args.warmup, 2)):
         loss = ts.step(batch)
     torch.cuda.synchronize()
-    t_est = time.perf_counter()
-    ts.step(batch)
-    torch.cuda.synchronize()
-    est = time.perf_counter() - t_est
-    elapsed, k = timed_steps(lambda: ts.step(batch), args.steps, dist, dev,
-                             est_steps=(int(args.min_timed_s / est) + 1) if args.min_timed_s > 0 else None)
+    est_steps = None
+    if args.min_timed_s > 0:
+        t_est = time.perf_counter()
+        ts.step(batch)
+        torch.cuda.synchronize()
+        est_steps = int(args.min_timed_s / (time.perf_counter() - t_est)) + 1
+    last = []
+
+    def run_step():
+        last[:] = [ts.step(batch)]                  # the loss of the last timed step (a device tensor: no sync)
+
+    elapsed, k = timed_steps(run_step, args.steps, dist, dev, est_steps=est_steps)
     ranks_ms = per_rank_ms(timed_steps.local_elapsed, k, dist, dev)
-    loss = float(ts.step(batch))
+    loss = float(last[0])
+    if args.dump_outputs and rank == 0:
+        params = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+        idx = torch.randint(0, params.numel(), (1 << 20,), generator=torch.Generator().manual_seed(0)).to(params.device)
+        dump_outputs(args.dump_outputs, {"loss": last[0].reshape(1), "params_sample": params[idx]})
+        del params
     if rank == 0:
         ranks = None
         if dist is not None:
@@ -822,13 +864,20 @@ def main():
     ap.add_argument("--engines", type=int, default=0,
                     help="engines (row ranges, one HIP stream each) per GPU; 0 = what generate_batch picks for the batch (2 from 512 rows up)")
     ap.add_argument("--window", type=int, default=None, help="state window of the decode loop (1 = immediate update K1d; default 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (sustained, roofline, other batches / shapes / dtypes, chunk "
+                         "kernels, vocoder, train step, CPU baseline); a plain run times the headline loop only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32; rank 0's rows when N > 1)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed decode loop (no secondary blocks): what a rocprofv3 trace of the headline should contain")
+                    help="with --full: only the timed decode loop (no secondary blocks): what a rocprofv3 trace of the headline "
+                         "should contain")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-chunk", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step measurement")
     args = ap.parse_args()
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_chunk = args.no_train = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -883,29 +932,79 @@ def main():
             eng.greedy_steps(96)
             torch.cuda.synchronize()
             n_pre += 96
-        t_est = time.perf_counter()                                  # step time estimate on the captured graph
-        eng.greedy_steps(48)
-        torch.cuda.synchronize()
-        est = (time.perf_counter() - t_est) / 48
-        k_run = max(args.steps, int(args.min_timed_s / est) + 1) if args.min_timed_s > 0 else args.steps
-        k_sus = max(args.steps, int(SUSTAINED_S / est) + 1)
+        k_run, k_sus = args.steps, 0
+        if args.min_timed_s > 0 or args.full:
+            t_est = time.perf_counter()                              # step time estimate on the captured graph
+            eng.greedy_steps(48)
+            torch.cuda.synchronize()
+            est = (time.perf_counter() - t_est) / 48
+            if args.min_timed_s > 0:
+                k_run = max(args.steps, int(args.min_timed_s / est) + 1)
+            if args.full:
+                k_sus = max(args.steps, int(SUSTAINED_S / est) + 1)
         if dist is not None:
             kk = torch.tensor([k_run, k_sus], device=dev, dtype=torch.int64)   # every rank sizes its token log for the same counts
             dist.all_reduce(kk, op=dist.ReduceOp.MAX)
             k_run, k_sus = int(kk[0].item()), int(kk[1].item())
-        # the loop generate_batch runs: picks, stop flags, the attention log and the next-token embedding inside the step
+        # the loop generate_batch runs: picks, stop flags, the attention log and the next-token embedding inside the step;
+        # from a zero recurrent state (the preheat ran for a wall time, not a step count), so that the outputs repeat
+        eng.reset()
         eng.begin_greedy(k_run + k_sus + args.warmup + 8, log_att=True)
         eng.greedy_steps(8)                                           # captures the multi-token graph (untimed)
         eng.greedy_steps(args.warmup)
         elapsed, k_run = timed_steps(lambda n: eng.greedy_steps(n), k_run, dist, dev, batched=True)
         ranks_ms = per_rank_ms(timed_steps.local_elapsed, k_run, dist, dev)
-        el_sus, k_sus = timed_steps(lambda n: eng.greedy_steps(n), k_sus, dist, dev, batched=True)   # secondary figure
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_step_outputs(eng.engines if n_eng > 1 else [eng]))
+        if k_sus:
+            el_sus, k_sus = timed_steps(lambda n: eng.greedy_steps(n), k_sus, dist, dev, batched=True)   # secondary figure
         toks = eng.greedy_tokens()
         assert toks.shape == (1, B, k_run + k_sus + args.warmup + 8)
         assert int(toks.min()) >= 0 and int(toks.max()) < 4099
 
         out = None
         if rank == 0:
+            # the step as a whole against HBM: recurrent state read + written once per block, every decode-time weight
+            # read once (the bytes the engine's packs actually hold), text-side K/V rows read once
+            ms_step = elapsed / k_run * 1e3
+            engs = eng.engines if n_eng > 1 else [eng]
+            parts_b = [step_hbm_bytes(e_) for e_ in engs]
+            s_bytes, kv_bytes, s_bytes_imm = (sum(p_[i] for p_ in parts_b) for i in (0, 2, 3))
+            w_bytes = parts_b[0][1] * (n_eng if B < 256 else 1)      # (packed weights are shared; at a large batch the second engine's reads hit the Infinity Cache or not: priced ONCE)
+            step_bytes = w_bytes + s_bytes + kv_bytes
+            step_roof = {"what": "whole decode step vs HBM: state read (+ write every W-th step) + decode-time weights + text K/V, per step per GPU",
+                         "immediate_form": {"what": "the same step priced with the state read AND written every token "
+                                                    "(SURVEY 8(d) / VERDICT r01 accounting: the bytes K1w avoids still counted)",
+                                            "bytes_per_step": w_bytes + s_bytes_imm + kv_bytes,
+                                            "frac": (w_bytes + s_bytes_imm + kv_bytes) / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                         "state_bytes": s_bytes, "weight_bytes": w_bytes, "text_kv_bytes": kv_bytes,
+                         "bytes_per_step": step_bytes, "ms_per_step": ms_step, "bound": "hbm",
+                         "achieved": step_bytes / (ms_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            out = {
+                "metric": "codec tokens/sec (whole node), 169M d1024xl12 batched greedy decode",
+                "value": total_rows * k_run / elapsed, "unit": "codec tokens/s", "n_gpus": world,
+                "steps": k_run, "steps_requested": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+                "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None,
+                "dtype": "bf16" if dtype == torch.bfloat16 else "f32", "data": "synthetic",
+                "config": {"workload": f"L169 greedy codec-token decode, B_total={total_rows} ({B} rows on this GPU" + (", fixed per GPU" if weak else f" = B_total / {world}") + "), "
+                                       f"T_txt={T_TXT}, H=4 Dk=Dv=256, 12+1 GLA blocks, fp32 recurrent state, "
+                                       f"{nparam / 1e6:.1f}M params, one hipGraph replay per {eng1.GRAPH_STEPS} tokens, state window {eng1.window}, "
+                                       + (f"{n_eng} engines of {B // n_eng} rows on {n_eng} HIP streams (shared packed weights)" if n_eng > 1
+                                          else "one engine"),
+                           "global_batch": total_rows, "rows_per_gpu": B, "engines_per_gpu": n_eng,
+                           "loop": "the device loop LinaModel.generate_batch runs (picks, stop flags, attention log, next-token "
+                                   "embedding inside the captured step)",
+                           "parallelism": f"batch-shard x{world} (no collective)",
+                           "timed_region": f"exactly {k_run} steps" + (f" (--min-timed-s {args.min_timed_s})" if args.min_timed_s > 0 else "")},
+                "min_timed_s": args.min_timed_s, "full": args.full,
+                "step_roofline": step_roof,
+            }
+            if dist is not None:
+                out["ranks"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "per_rank_ms": ranks_ms,
+                                "collectives_in_timed_region": "barrier only (batch shard, no data-path collective)",
+                                "rccl": rccl_summary()}
+        if rank == 0 and args.full:
             P = eng1.packs[0]
             k1_b2b, k1_entry = measure_k1(eng1)                    # back to back with itself (conservative)
             k1_dt, k1_n, ms_with, ms_without = eng1.time_update_kernel()   # (two engines: in ONE engine's step graph, the other idle)
@@ -946,48 +1045,9 @@ def main():
                                                   "every step) over the same time: the traffic this kernel avoids",
                                           "bytes_per_launch": k1d_bytes,
                                           "equivalent_GBs": k1d_bytes / k1_dt / 1e9}
-            # the step as a whole against HBM: recurrent state read + written once per block, every decode-time weight
-            # read once (the bytes the engine's packs actually hold), text-side K/V rows read once
-            ms_step = elapsed / k_run * 1e3
-            engs = eng.engines if n_eng > 1 else [eng]
-            parts_b = [step_hbm_bytes(e_) for e_ in engs]
-            s_bytes, kv_bytes, s_bytes_imm = (sum(p_[i] for p_ in parts_b) for i in (0, 2, 3))
-            w_bytes = parts_b[0][1] * (n_eng if B < 256 else 1)      # (packed weights are shared; at a large batch the second engine's reads hit the Infinity Cache or not: priced ONCE)
-            step_bytes = w_bytes + s_bytes + kv_bytes
-            step_roof = {"what": "whole decode step vs HBM: state read (+ write every W-th step) + decode-time weights + text K/V, per step per GPU",
-                         "immediate_form": {"what": "the same step priced with the state read AND written every token "
-                                                    "(SURVEY 8(d) / VERDICT r01 accounting: the bytes K1w avoids still counted)",
-                                            "bytes_per_step": w_bytes + s_bytes_imm + kv_bytes,
-                                            "frac": (w_bytes + s_bytes_imm + kv_bytes) / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                         "state_bytes": s_bytes, "weight_bytes": w_bytes, "text_kv_bytes": kv_bytes,
-                         "bytes_per_step": step_bytes, "ms_per_step": ms_step, "bound": "hbm",
-                         "achieved": step_bytes / (ms_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
-            out = {
-                "metric": "codec tokens/sec (whole node), 169M d1024xl12 batched greedy decode",
-                "value": total_rows * k_run / elapsed, "unit": "codec tokens/s", "n_gpus": world,
-                "steps": k_run, "steps_requested": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-                "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None,
-                "dtype": "bf16" if dtype == torch.bfloat16 else "f32", "data": "synthetic",
-                "config": {"workload": f"L169 greedy codec-token decode, B_total={total_rows} ({B} rows on this GPU" + (", fixed per GPU" if weak else f" = B_total / {world}") + "), "
-                                       f"T_txt={T_TXT}, H=4 Dk=Dv=256, 12+1 GLA blocks, fp32 recurrent state, "
-                                       f"{nparam / 1e6:.1f}M params, one hipGraph replay per {eng1.GRAPH_STEPS} tokens, state window {eng1.window}, "
-                                       + (f"{n_eng} engines of {B // n_eng} rows on {n_eng} HIP streams (shared packed weights)" if n_eng > 1
-                                          else "one engine"),
-                           "global_batch": total_rows, "rows_per_gpu": B, "engines_per_gpu": n_eng,
-                           "loop": "the device loop LinaModel.generate_batch runs (picks, stop flags, attention log, next-token "
-                                   "embedding inside the captured step)",
-                           "parallelism": f"batch-shard x{world} (no collective)",
-                           "timed_region": f"exactly {k_run} steps" + (f" (--min-timed-s {args.min_timed_s})" if args.min_timed_s > 0 else "")},
-                "min_timed_s": args.min_timed_s,
-                "sustained": {"what": f"the same loop over >= {SUSTAINED_S} s right after the timed region (secondary; not `value`)",
-                              "steps": k_sus, "ms_per_step": el_sus / k_sus * 1e3, "tokens_per_s": total_rows * k_sus / el_sus},
-                "roofline": roof, "step_roofline": step_roof,
-            }
-            if dist is not None:
-                out["ranks"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "per_rank_ms": ranks_ms,
-                                "collectives_in_timed_region": "barrier only (batch shard, no data-path collective)",
-                                "rccl": rccl_summary()}
+            out["sustained"] = {"what": f"the same loop over >= {SUSTAINED_S} s right after the timed region (secondary; not `value`)",
+                                "steps": k_sus, "ms_per_step": el_sus / k_sus * 1e3, "tokens_per_s": total_rows * k_sus / el_sus}
+            out["roofline"] = roof
             # secondary, untimed-region measurements (rank 0 only): the default sampling mode of the reference
             # (top-k 100, temperature) through the same graph, K2 / K2b at the training shape
             if world == 1 and not args.headline_only:

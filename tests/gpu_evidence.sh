@@ -6,8 +6,9 @@
 #   <tag>_k2b_kernel_stats.csv, <tag>_k2b_traffic.json                    K2b (three sweeps) at B=64, H=4, T=4096
 # Counters are collected in their own runs with --kernel-trace only (MI355X_MICROARCH.md, HBM / rocprofv3 section).
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+OUT=${BENCH_OUT:-bench_out}; mkdir -p "$OUT"       # where the bench.py lines of this session write
 TAG=${1:-r04}
-rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/kp -o kp -- python bench.py --steps 300 --warmup 16 --no-train --no-cpu-baseline --no-chunk > gpurun_out/${TAG}_bench_prof.log 2>&1; echo "bench_prof=$?"
+rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/kp -o kp -- python bench.py --full --steps 300 --warmup 16 --no-train --no-cpu-baseline --no-chunk > "$OUT"/${TAG}_bench_prof.log 2>&1; echo "bench_prof=$?"
 db=$(find /tmp/kp -name "*results.db" | head -1)
 python tools/prof_summary.py $db gpurun_out/${TAG}_bench_kernel_stats.csv > /dev/null
 python tools/prof_step_timeline.py $db gpurun_out/${TAG}_step_timeline.csv > gpurun_out/${TAG}_step_timeline.txt; head -2 gpurun_out/${TAG}_step_timeline.txt

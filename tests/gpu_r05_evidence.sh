@@ -1,10 +1,11 @@
 #!/bin/bash
 # round 5 evidence session: smoke, the driver's bench command, K1w traffic at B = 512, SQ counters of the CURRENT K2 / K2b / K1w
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+OUT=${BENCH_OUT:-bench_out}; mkdir -p "$OUT"       # where the bench.py lines of this session write
 TAG=${1:-r05}
 timeout 300 python __graft_entry__.py --smoke > gpurun_out/${TAG}_smoke.log 2>&1; echo "smoke=$?"; tail -1 gpurun_out/${TAG}_smoke.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; echo "bench=$?"; tail -2 gpurun_out/${TAG}_bench.err
-python tools/bench_summary.py gpurun_out/${TAG}_bench.json
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT"/${TAG}_bench.json 2> "$OUT"/${TAG}_bench.err; echo "bench=$?"; tail -2 "$OUT"/${TAG}_bench.err
+python tools/bench_summary.py "$OUT"/${TAG}_bench.json
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/k1_$C; K1_B=512 K1_REPS=8 timeout 300 rocprofv3 --kernel-trace --pmc $C -d /tmp/k1_$C -o k1 --output-format csv -- python tools/perf_k1w.py > gpurun_out/${TAG}_k1w_b512_$C.log 2>&1; echo "k1w b512 $C=$?"
 done

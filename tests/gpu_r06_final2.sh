@@ -8,6 +8,7 @@
 # the b = 8 segment-parallel forward / backward; SQ counters of K2 / K2b / K1w / the tall projections; and the LINA_DMA_NT A/B on
 # K2b and the b = 8 passes.
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+OUT=${BENCH_OUT:-bench_out}; mkdir -p "$OUT"       # where the bench.py lines of this session write
 TAG=${1:-r06}
 timeout 300 python __graft_entry__.py --smoke > gpurun_out/${TAG}_smoke.log 2>&1; echo "smoke=$?"; tail -1 gpurun_out/${TAG}_smoke.log
 LINA_PARITY_TAG=$TAG timeout 1800 python -m pytest tests -m gpu -q --timeout=900 > gpurun_out/${TAG}_pytest_gpu.log 2>&1; echo "pytest=$?"; tail -4 gpurun_out/${TAG}_pytest_gpu.log
@@ -54,9 +55,9 @@ python tools/pmc_sq.py gpurun_out/${TAG}_k1w_sq.json "K1w + K5 B=256|gla_decode_
 python tools/pmc_sq.py gpurun_out/${TAG}_tall_sq.json "inproj|gla_inproj_tall_kernel" "up / head|linear_tall_kernel" -- /tmp/sq_tall_1 /tmp/sq_tall_2
 # ---- the bench line quotes the counter summaries above: put them where bench.py reads them (the same files are committed)
 cp gpurun_out/${TAG}_*traffic*.json gpurun_out/${TAG}_*_sq.json profiles/ 2>/dev/null
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; echo "bench=$?"; tail -2 gpurun_out/${TAG}_bench.err
-python tools/bench_summary.py gpurun_out/${TAG}_bench.json
-rm -rf /tmp/kp; timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kp -o kp -- python bench.py --steps 300 --warmup 16 --no-train --no-cpu-baseline --no-chunk > gpurun_out/${TAG}_bench_prof.log 2>&1; echo "bench_prof=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT"/${TAG}_bench.json 2> "$OUT"/${TAG}_bench.err; echo "bench=$?"; tail -2 "$OUT"/${TAG}_bench.err
+python tools/bench_summary.py "$OUT"/${TAG}_bench.json
+rm -rf /tmp/kp; timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kp -o kp -- python bench.py --full --steps 300 --warmup 16 --no-train --no-cpu-baseline --no-chunk > "$OUT"/${TAG}_bench_prof.log 2>&1; echo "bench_prof=$?"
 db=$(find /tmp/kp -name "*results.db" | head -1)
 python tools/prof_summary.py $db gpurun_out/${TAG}_bench_kernel_stats.csv
 python tools/prof_step_timeline.py $db gpurun_out/${TAG}_step_timeline.csv > gpurun_out/${TAG}_step_timeline.txt; head -8 gpurun_out/${TAG}_step_timeline.txt
