@@ -51,9 +51,11 @@ class _TrainAttentionFunction(torch.autograd.Function):
     def forward(ctx, q, k, v, mask):
         scale = 1.0 / math.sqrt(q.shape[-1])
         s = _mm_f32(q, k.transpose(-2, -1)) * scale                       # [B, T, S] fp32
+        w = torch.softmax(s if mask is None else s.masked_fill(~mask, float("-inf")), dim=-1)
         if mask is not None:
-            s = s.masked_fill(~mask, float("-inf"))
-        w = torch.softmax(s, dim=-1)
+            # a query row with no attendable position: softmax over all -inf is NaN, SDPA gives 0 (and 0 gradients) -- the
+            # zeroed row is also what backward sees, so its ds is 0 instead of NaN spread over every shared operand
+            w = w.masked_fill(~mask.any(-1, keepdim=True), 0.0)
         wb = w.to(v.dtype)
         out = torch.matmul(wb, v)                                         # [B, T, dv] (v [1, S, dv]: one GEMM over B T rows)
         ctx.save_for_backward(q, k, v, w)
@@ -108,9 +110,16 @@ def train_attention(q, k, v, mask=None, dropout_p: float = 0.0):
     with torch.autocast(q.device.type, enabled=False):
         qf, kf, vf = q.float(), k.float(), v.float()
         w = torch.matmul(qf, kf.transpose(-2, -1)) * (1.0 / math.sqrt(q.size(-1)))
-        if mask is not None:
-            w = w.masked_fill(~mask, float("-inf")) if mask.dtype == torch.bool else w + mask
+        live = None
+        if mask is not None and mask.dtype == torch.bool:
+            # a fully masked row is left unmasked for the softmax (finite, so its backward is too) and zeroed after it, as SDPA
+            live = mask.any(-1, keepdim=True)
+            w = w.masked_fill(~(mask | ~live), float("-inf"))
+        elif mask is not None:
+            w = w + mask
         w = torch.softmax(w, dim=-1)
+        if live is not None:
+            w = w.masked_fill(~live, 0.0)
         if dropout_p > 0.0:
             w = torch.dropout(w, dropout_p, True)
         return torch.matmul(w, vf).to(cd)

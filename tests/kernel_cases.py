@@ -41,8 +41,67 @@ def assert_close(got, ref, rel, what):
     assert err <= rel, f"{what}: max rel err {err:.3e} > {rel:.1e}"
 
 
-def make_gla_inputs(B, H, T, Dk, Dv, dtype, dev, seed=0, resets=False):
-    """``resets``: False | True (reset gates, a cut-forcing run of them, one gate beyond the clamp) | "saturated" (see below)."""
+class LibCalls:
+    """Call-recording proxy around the active backend's C library: every ``lib.<symbol>(...)`` made while it is installed is
+    logged as (symbol, args) and then forwarded unchanged.  ``with LibCalls() as calls:`` installs it through
+    ``ops.set_backend`` (the launchers look the backend up per call) and restores the previous backend on exit."""
+
+    def __init__(self):
+        self.calls = []
+        self._prev = None
+
+    def __enter__(self):
+        self._prev = ops.get_backend()
+        prev, calls = self._prev, self.calls
+
+        class _Lib:
+            def __getattr__(_, name):
+                fn = getattr(prev.lib, name)
+                if not callable(fn):
+                    return fn
+
+                def rec(*args):
+                    calls.append((name, args))
+                    return fn(*args)
+                return rec
+
+        class _Spy:
+            name = prev.name
+            lib = _Lib()
+            require = staticmethod(prev.require)
+            stream = staticmethod(prev.stream)
+
+        ops.set_backend(_Spy())
+        return self
+
+    def __exit__(self, *exc):
+        ops.set_backend(self._prev)
+        return False
+
+    def of(self, name):
+        return [a for n, a in self.calls if n == name]
+
+
+# argument positions in the C ABI (include/lina_gla.h): workspace and nseg of lina_gla_chunk_fwd_seg; seg_states and nseg of
+# lina_gla_chunk_bwd_full
+_FWD_SEG_WS, _FWD_SEG_NSEG = 7, 8
+_BWD_FULL_SEG_STATES, _BWD_FULL_NSEG = 14, 15
+
+
+def seg_len(T, nseg):
+    """Tokens per segment of the segment-parallel K2 / K2b for ``nseg`` requested segments (lina_gla_chunk_fwd_seg: whole
+    32-token chunks) and the number of segments that hold tokens."""
+    tseg = ((T + nseg - 1) // nseg + 31) // 32 * 32
+    return tseg, (T + tseg - 1) // tseg
+
+
+def make_gla_inputs(B, H, T, Dk, Dv, dtype, dev, seed=0, resets=False, nseg=None):
+    """``resets``: False | True (reset gates, a cut-forcing run of them, one gate beyond the clamp) | "saturated" (see below) |
+    "rows": different reset positions in every batch row, placed against the segments of ``nseg`` (default: the launch
+    policy's choice for B*H heads) -- row b % 3 == 0: a run of resets straddling every interior segment boundary (s Tseg - 1,
+    s Tseg, s Tseg + 1; all channels at one boundary, a row-dependent third of them at the next) plus one at a row-dependent
+    token; b % 3 == 1: a cut-forcing run (-3 on every channel of every token: -96 per chunk) filling one whole segment, so
+    that segment's boundary state must come out exactly decayed, plus one reset at a row-dependent token; b % 3 == 2: none."""
     g = torch.Generator().manual_seed(seed)
     # projections arrive as [B,T,H*D]; the ops see the head-first VIEW (reference gla.py:173)
     def heads(x):
@@ -51,7 +110,7 @@ def make_gla_inputs(B, H, T, Dk, Dv, dtype, dev, seed=0, resets=False):
     k = torch.randn(B, T, H * Dk, generator=g).to(dtype)
     v = torch.randn(B, T, H * Dv, generator=g).to(dtype)
     gk = (F.logsigmoid(torch.randn(B, T, H * Dk, generator=g) * 2.0) / 4.0)
-    if resets:
+    if resets and resets != "rows":
         gk[:, 5:9] = -20.0          # 4 consecutive resets: 80 > 60 forces a chunk cut
         gk[:, 17, ::3] = -20.0
         gk[:, 23, 1::2] = -70.0     # single gate beyond the clamp
@@ -63,6 +122,21 @@ def make_gla_inputs(B, H, T, Dk, Dv, dtype, dev, seed=0, resets=False):
             t0 = T - T % 32
             gk[:, t0:] = 0.0
             gk[:, t0 + 1, 1::4] = -75.0
+    if resets == "rows":
+        tseg, ns = seg_len(T, ops.chunk_segments(B * H, T) if nseg is None else nseg)
+        gk = gk.view(B, T, H, Dk)
+        for b in range(B):
+            kind = b % 3
+            if kind == 0:
+                for s_ in range(1, ns):
+                    sl = slice(None) if s_ % 2 else slice((b // 3) % 3, None, 3)
+                    gk[b, s_ * tseg - 1:s_ * tseg + 2, :, sl] = -20.0
+            elif kind == 1:
+                s_ = (1 + b // 3) % ns if ns > 1 else 0
+                gk[b, s_ * tseg:min(T, (s_ + 1) * tseg)] = -3.0
+            if kind != 2:
+                gk[b, (7 + 13 * b) % T, b % H] = -20.0
+        gk = gk.view(B, T, H * Dk)
     gk = gk.to(dtype)
     h0 = torch.randn(B, H, Dk, Dv, generator=g) * 0.5
     return [heads(x.to(dev)) for x in (q, k, v, gk)] + [h0.to(dev)]
@@ -143,16 +217,30 @@ def check_chunk_dv512_one_launch(dev, monkeypatch, B, H, T, oracle=True):
         assert_close(S1, rS, 1e-2, "K2 (256 x 512, one launch) state")
 
 
-def check_chunk_segmented(dev, B, H, T, nseg, resets=False, D=256):
+def check_chunk_segmented(dev, B, H, T, nseg, resets=False, D=256, expect_nseg=None):
     """Segment-parallel K2 (state-only pass + combine + full pass) == the fp64 recurrent oracle and == the plain
     one-workgroup-per-head(-group) kernel, with and without an initial state; bf16, Dk = Dv = D (256, or 128 / 64 with
-    2 / 4 heads per workgroup)."""
+    2 / 4 heads per workgroup).  Every batch row's output and final state are held to the tolerance of their OWN scale (a
+    slot-indexing error in the batch term shows in one row).  ``nseg=None``: the launch policy's choice, which must be
+    ``expect_nseg`` segments of the segmented kernel."""
     dtype = torch.bfloat16
-    q, k, v, gk, h0 = make_gla_inputs(B, H, T, D, D, dtype, dev, seed=21, resets=resets)
+    q, k, v, gk, h0 = make_gla_inputs(B, H, T, D, D, dtype, dev, seed=21, resets=resets,
+                                      nseg=expect_nseg if nseg is None else nseg)
     ro, rS = oracle_gla(q, k, v, gk, h0)
-    o, S = ops.chunk_gla(q, k, v, gk, initial_state=h0, output_final_state=True, nseg=nseg)
+    with LibCalls() as calls:
+        o, S = ops.chunk_gla(q, k, v, gk, initial_state=h0, output_final_state=True, nseg=nseg)
+    launched = [int(a[_FWD_SEG_NSEG]) for a in calls.of("lina_gla_chunk_fwd_seg")]
+    if expect_nseg is not None:
+        assert launched == [expect_nseg], f"segment-parallel K2 launches {launched}, expected one with nseg={expect_nseg}"
+    elif nseg is not None and nseg > 1:
+        assert launched == [nseg], f"segment-parallel K2 launches {launched}"
+    nseg = launched[0] if launched else 1
     assert_close(o, ro, tol_out(dtype, chunk=True), f"K2 segmented o (nseg={nseg})")
     assert_close(S, rS, 1e-2, "K2 segmented state")
+    if B > 1:
+        for b in range(B):
+            assert_close(o[b], ro[b], tol_out(dtype, chunk=True), f"K2 segmented o, batch row {b} (B={B}, nseg={nseg})")
+            assert_close(S[b], rS[b], 1e-2, f"K2 segmented final state, batch row {b} (B={B}, nseg={nseg})")
     o1, S1 = ops.chunk_gla(q, k, v, gk, initial_state=h0, output_final_state=True, nseg=1)
     assert_close(o.float(), o1.float(), 2e-2, "K2 segmented vs plain")
     o2, S2 = ops.chunk_gla(q, k, v, gk, nseg=nseg)
@@ -241,12 +329,15 @@ def check_chunk_bwd_long(dev, B, H, T, Dk, Dv, dtype, reset_every=512, with_h0=T
         assert_close(lh0.grad, rdh0, 1e-2 if dtype == torch.bfloat16 else 5e-4, f"K2b dh0 (T={T})")
 
 
-def check_chunk_bwd_full(dev, B, H, T, D, nseg, resets=False, with_h0=True, with_dht=True, seed=5):
+def check_chunk_bwd_full(dev, B, H, T, D, nseg, resets=False, with_h0=True, with_dht=True, seed=5, via_autograd=False):
     """K2b on the full-head kernel (lina_gla_chunk_bwd_full: reverse sweep -> dv, value-gated sweeps -> dq / dk + dg, ``nseg``
     sequence segments from boundary states) called directly, against torch autograd through the fp64 recurrent oracle.
-    bf16 I/O: 2e-2 of max|ref| per tensor (4e-2 for dg at T >= 2048, see check_chunk_bwd_long)."""
+    bf16 I/O: 2e-2 of max|ref| per tensor (4e-2 for dg at T >= 2048, see check_chunk_bwd_long); at B > 1 every batch row
+    against its own scale as well.  ``via_autograd``: the same inputs once more through ``ops.chunk_gla`` autograd at ``nseg``
+    -- the forward's segment start states must be handed to K2b (the seg_states pointer of lina_gla_chunk_bwd_full is the
+    workspace lina_gla_chunk_fwd_seg wrote) -- against the same oracle gradients and against the nseg = 1 single pass."""
     dtype = torch.bfloat16
-    q, k, v, gk, h0 = make_gla_inputs(B, H, T, D, D, dtype, dev, seed=seed, resets=resets)
+    q, k, v, gk, h0 = make_gla_inputs(B, H, T, D, D, dtype, dev, seed=seed, resets=resets, nseg=nseg)
     if not with_h0:
         h0 = None
     g = torch.Generator().manual_seed(seed + 1)
@@ -270,10 +361,42 @@ def check_chunk_bwd_full(dev, B, H, T, D, nseg, resets=False, with_h0=True, with
     else:
         refs, rdh0, _ = oracle_gla_grads_long(q, k, v, gk, h0, d_o, d_ht)
     tol_g = 4e-2 if T >= 2048 else 2e-2
-    for name, a, r in zip(("dq", "dk", "dv", "dg"), (dq, dk, dv, dg), refs):
-        assert_close(a, r, tol_g if name == "dg" else 2e-2, f"K2b(full, nseg={nseg}) {name}")
-    if h0 is not None:
-        assert_close(dh0, rdh0, 1e-2, f"K2b(full, nseg={nseg}) dh0")
+
+    def compare(got, what):
+        for name, a, r in zip(("dq", "dk", "dv", "dg", "dh0"), got, list(refs) + [rdh0]):
+            if name == "dh0" and h0 is None:
+                continue
+            tol = 1e-2 if name == "dh0" else tol_g if name == "dg" else 2e-2
+            assert_close(a, r, tol, f"{what} {name}")
+            if B > 1:
+                for b in range(B):
+                    assert_close(a[b], r[b], tol, f"{what} {name}, batch row {b}")
+
+    compare((dq, dk, dv, dg, dh0), f"K2b(full, nseg={nseg})")
+    if not via_autograd:
+        return
+    grads = {}
+    for ns in (nseg, 1):
+        leaves = [x.detach().clone().requires_grad_(True) for x in (q, k, v, gk)]
+        lh0 = None if h0 is None else h0.detach().clone().requires_grad_(True)
+        with LibCalls() as calls:
+            o, S = ops.chunk_gla(*leaves, scale=scale, initial_state=lh0, output_final_state=with_dht, nseg=ns)
+            loss = (o.float() * d_o.float()).sum()
+            if with_dht:
+                loss = loss + (S * d_ht).sum()
+            loss.backward()
+        fwd, bwd = calls.of("lina_gla_chunk_fwd_seg"), calls.of("lina_gla_chunk_bwd_full")
+        assert len(bwd) == 1 and int(bwd[0][_BWD_FULL_NSEG]) == ns, [int(a[_BWD_FULL_NSEG]) for a in bwd]
+        if ns > 1:
+            assert len(fwd) == 1 and int(fwd[0][_FWD_SEG_NSEG]) == ns, "the forward did not run segment-parallel"
+            handed = bwd[0][_BWD_FULL_SEG_STATES].value
+            assert handed and handed == fwd[0][_FWD_SEG_WS].value, "K2b did not get the forward's segment start states"
+        grads[ns] = [x.grad for x in leaves] + [None if lh0 is None else lh0.grad]
+        compare(grads[ns], f"K2b via chunk_gla autograd (nseg={ns})")
+    for name, a, r in zip(("dq", "dk", "dv", "dg", "dh0"), grads[nseg], grads[1]):
+        if r is not None:
+            assert_close(a.float(), r.float(), tol_g if name == "dg" else 2e-2,
+                         f"K2b via chunk_gla autograd: nseg={nseg} vs the single pass, {name}")
 
 
 def check_chunk_simple(dev, B, H, T, Dk, Dv, dtype, with_h0=True):
@@ -1752,3 +1875,58 @@ def check_istft_ola(dev, B, T, win, hop):
     if rec.shape[1] <= 2 * win:
         return
     assert (rec[:, inner] - sig[:, pad:pad + rec.shape[1]][:, inner]).abs().max() < 1e-4, "K9 does not invert the STFT framing"
+
+
+def check_train_attention_masked_rows(dev, B=3, T=37, S=11, d=128):
+    """``blind_attention.train_attention`` (the training cross-attention) == ``F.scaled_dot_product_attention`` on ragged boolean
+    masks that hold fully masked query rows -- what a collate that builds x_mask (x) y_mask without unmasking text position 0
+    gives every padded codec position: SDPA returns 0 there and finite gradients, so must we.  k / v with batch 1 (the shared
+    positional table) and with batch B (per-row text), in every pairing the blind cross-attention uses.
+      fp32: output and the gradients of q, k, v against fp64 SDPA on the same inputs, 1e-5 of max|ref|;
+      bf16 (autocast on a device, bf16 tensors on the CPU): against fp32-input SDPA (in fp64) on the bf16-rounded inputs,
+      2e-2 of max|ref| (bf16 I/O)."""
+    from lina_speech_amd.blind_attention import train_attention
+    g = torch.Generator().manual_seed(17)
+    xlen, ylen = [S, 4, 1][:B] + [S] * max(0, B - 3), [T, 20, 9][:B] + [T] * max(0, B - 3)
+    mask = torch.zeros(B, 1, T, S, dtype=torch.bool)
+    for b in range(B):
+        mask[b, 0, :ylen[b], :xlen[b]] = True
+    mask[0, 0, 3] = False                                      # and one fully masked row inside a full-length row
+    assert (~mask.any(-1)).sum() > 0
+    mask = mask.to(dev)
+    d_o = torch.randn(B, 1, T, d, generator=g).to(dev)
+    for kb, vb in ((1, 1), (B, B), (B, 1), (1, B)):
+        q = torch.randn(B, 1, T, d, generator=g)
+        k = torch.randn(kb, 1, S, d, generator=g)
+        v = torch.randn(vb, 1, S, d, generator=g)
+        for dtype in (torch.float32, torch.bfloat16):
+            xs = [x.to(dtype).float() for x in (q, k, v)]            # what the kernel sees (bf16: rounded first)
+            if dev == "cpu":                                         # (no autocast on the host path: the tensors' dtype)
+                leaves = [x.to(dtype).detach().clone().requires_grad_(True) for x in xs]
+                o = train_attention(*leaves, mask)
+            else:
+                leaves = [x.to(dev).detach().clone().requires_grad_(True) for x in xs]
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=dtype == torch.bfloat16):
+                    o = train_attention(*leaves, mask)
+            (o.float() * d_o).sum().backward()
+            rl = [x.detach().to(F64).requires_grad_(True) for x in xs]
+            ro = F.scaled_dot_product_attention(rl[0], rl[1].expand(B, -1, -1, -1), rl[2].expand(B, -1, -1, -1),
+                                                attn_mask=mask.cpu())
+            (ro * d_o.cpu().to(F64)).sum().backward()
+            tol = 1e-5 if dtype == torch.float32 else 2e-2
+            tag = f"train attention vs SDPA, fully masked rows ({str(dtype)[6:]}, k batch {kb}, v batch {vb})"
+            assert_close(o, ro, tol, f"{tag}: out")
+            assert float(o.detach().float()[~mask.any(-1)].abs().max()) == 0.0, "a fully masked row is not 0"
+            for name, a, r in zip(("dq", "dk", "dv"), leaves, rl):
+                assert a.grad is not None and a.grad.shape == r.grad.shape, name
+                assert_close(a.grad, r.grad, tol, f"{tag}: {name}")
+    # two heads: not the one-head form of the fast path -- the written-out fallback, fp32
+    xs = [torch.randn(B, 2, n, d, generator=g) for n in (T, S, S)]
+    leaves = [x.to(dev).clone().requires_grad_(True) for x in xs]
+    o = train_attention(*leaves, mask)
+    (o.float() * d_o).sum().backward()
+    rl = [x.to(F64).requires_grad_(True) for x in xs]
+    ro = F.scaled_dot_product_attention(*rl, attn_mask=mask.cpu())
+    (ro * d_o.cpu().to(F64)).sum().backward()
+    for name, a, r in zip(("out", "dq", "dk", "dv"), [o] + [x.grad for x in leaves], [ro] + [x.grad for x in rl]):
+        assert_close(a, r, 1e-5, f"train attention (written-out form, 2 heads) vs SDPA, fully masked rows: {name}")

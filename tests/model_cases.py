@@ -776,3 +776,219 @@ def check_config5_slice_golden(dev, dtype=torch.float32, rel_loss=2e-4, rel_grad
             bad.append((grp, w, tol_max, tol_norm))
     record_parity(f"{tag}: analytically zero gradient tensors (noise on both sides)", n_zero, None)
     assert not bad, bad
+
+
+def collate_like_reference(rows, all_false_rows: bool = False):
+    """A padded batch with the mask semantics of the reference's ``simple_collate`` (initial_state.py): ``rows`` = [(text ids
+    [n_txt], codec ids [n, 1]), ...] -> (x, y, encoder_mask, crossatt_mask, logits_mask): text and codes padded with 0,
+    encoder_mask = x_mask (x) x_mask, crossatt_mask = x_mask (x) y_mask with text position 0 unmasked in every row, logits_mask =
+    y_mask.  ``all_false_rows``: position 0 NOT unmasked -- every padded codec position then has a query row with nothing to
+    attend (what a collate without that line gives)."""
+    from torch.nn.utils.rnn import pad_sequence
+    xlen = torch.tensor([len(t) for t, _ in rows])
+    ylen = torch.tensor([len(c) for _, c in rows])
+    x_mask = torch.arange(int(xlen.max()))[None, :] < xlen[:, None]
+    y_mask = torch.arange(int(ylen.max()))[None, :] < ylen[:, None]
+    x = pad_sequence([t for t, _ in rows], batch_first=True, padding_value=0)
+    y = pad_sequence([c for _, c in rows], batch_first=True, padding_value=0)
+    encoder_mask = x_mask[:, None, :] & x_mask[:, :, None]
+    crossatt_mask = x_mask[:, None, :] & y_mask[:, :, None]
+    if not all_false_rows:
+        crossatt_mask[:, :, 0] = True
+    return x, y, encoder_mask, crossatt_mask, y_mask
+
+
+# ragged codec lengths of the padded-batch check (BOS included, so a row of n codes has n - 1 inputs / targets): the full 4097,
+# lengths that are not multiples of 32, one row below 1024 (its b = 1 run takes the plain chunk kernel), one very short row;
+# text lengths ragged within a padded width of 64
+PADDED_CODE_LENS = (4097, 2731, 4097, 1500, 3333, 700, 4090, 9, 4097, 3900, 2222, 1025, 4097, 64, 3000, 4097)
+PADDED_TEXT_LENS = (64, 50, 37, 64, 12, 20, 45, 3, 64, 31, 7, 64, 55, 1, 40, 26)
+
+
+def padded_rows(b, seed=53):
+    g = torch.Generator().manual_seed(seed)
+    return [(torch.randint(3, 256, (PADDED_TEXT_LENS[i],), generator=g),
+             structured_targets(1, PADDED_CODE_LENS[i], 4099, seed=seed + i)[0]) for i in range(b)]
+
+
+def _train_grads(model, inputs, dtype):
+    """Loss and {name: fp32 gradient} of one teacher-forced step (fp32, or under bf16 autocast: the way training runs)."""
+    x, y, em, cm, lm = inputs
+    model.zero_grad(set_to_none=True)
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=dtype == torch.bfloat16):
+        _, loss, _, _, _ = model(x, y, em, cm, logits_mask=lm)
+    loss.backward()
+    return float(loss.detach()), {n: p.grad.detach().float().clone() for n, p in model.named_parameters()}
+
+
+def _rows_alone(model, batch, dev, dtype):
+    """Every row of the padded batch alone at b = 1 -- codes truncated to its own length (every op along the code axis is
+    causal), text at the padded width (ConvPos's 'same' convolution makes the positional table depend on the text width).
+    Returns the rows' counted targets c_i (masked in, != the ignored class 1) and their (loss, grads)."""
+    x, y, em, cm, lm = batch
+    counts, per_row = [], []
+    for i in range(x.shape[0]):
+        n = int(lm[i].sum())
+        counts.append(int((lm[i, 1:n] & (y[i, 1:n, 0] != 1)).sum()))
+        inputs = (x[i:i + 1], y[i:i + 1, :n], em[i:i + 1], cm[i:i + 1, :n], lm[i:i + 1, :n])
+        per_row.append(_train_grads(model, tuple(t.to(dev) for t in inputs), dtype))
+    return counts, per_row
+
+
+def _weighted(counts, per_row, override=None):
+    """The rows combined as the batch's token mean combines them: sum_i (c_i / C) x (loss_i, grad_i).  ``override``: {row: c}
+    for the negative controls (0 drops the row)."""
+    cs = [float(c) for c in counts]
+    for i, c in (override or {}).items():
+        cs[i] = float(c)
+    C = sum(cs)
+    loss = sum(c / C * li for c, (li, _) in zip(cs, per_row))
+    grads = {n: sum(c / C * gi[n].double() for c, (_, gi) in zip(cs, per_row) if c) for n in per_row[0][1]}
+    return loss, grads
+
+
+def _max_rel_errors(grads, ref, zero_tol):
+    """Per tensor max|got - ref| / max|ref|; analytically-zero tensors (max|ref| < 1e-5 of the largest: rounding noise) only
+    need ``got`` to be noise too (as grad_errors_by_group).  Returns ({name: err}, [zero names])."""
+    largest = max(float(r.abs().max()) for r in ref.values())
+    errs, zeros = {}, []
+    for name, r in ref.items():
+        a = grads[name].double()
+        assert torch.isfinite(a).all(), f"{name}: non-finite gradient"
+        rm = float(r.abs().max())
+        if rm < 1e-5 * largest:
+            assert float(a.abs().max()) < zero_tol * largest, (name, float(a.abs().max()), largest)
+            zeros.append(name)
+            continue
+        errs[name] = float((a - r).abs().max()) / rm
+    return errs, zeros
+
+
+def check_padded_batch_equals_rows(dev, b=8, dtype=torch.float32, rel_grad=1e-3, rel_loss=1e-5, mask_forms=True,
+                                   max_cos_gap=0.02, max_norm_gap=0.04, med_cos_gap=0.003, med_norm_gap=0.01):
+    """A train step on a PADDED multi-row batch (the form training always takes) equals its rows: config-5 slice (the model of
+    the T = 4096 goldens, bigram targets), b rows with ragged code and text lengths collated as the reference collates them
+    (collate_like_reference), against each row alone at b = 1 -- the path pinned to the reference's autograd at T = 4096 --
+    (_rows_alone) combined as the batch's token mean combines them (_weighted).
+      fp32: loss within ``rel_loss`` and every parameter gradient within ``rel_grad`` of max|reference| per tensor; negative
+      controls (one row dropped, rows weighted equally instead of by their targets) must FAIL that bound.  The two sides
+      differ only in summation order (GEMM shapes, token splits), yet measured 6.6e-4 on one tensor: the input embedding,
+      whose rows each sum a handful of tokens' gradients, so one token's rounding difference -- amplified by the gated
+      recurrence at that position -- shows undiluted (every other element of that tensor within 1.7e-4);
+      bf16 autocast: batch and per-row bf16 combination each against the fp32 per-row combination, per tensor cosine and
+      norm error.  The gradients of this random-init slice are noisy in bf16 (cosines 0.93-0.98 with the fp32 rows, norms
+      inflated by that noise), and two runs of the same batch differ by up to 0.01 in cosine and 0.03 in norm error on the
+      small tensors (biases, norm gains): per tensor the batch's cosine at most ``max_cos_gap`` below the rows' and its norm
+      error at most ``max_norm_gap`` above; over all tensors the MEDIAN gaps within ``med_cos_gap`` / ``med_norm_gap`` (a
+      batching error moves every tensor at once); the rows weighted equally must fail these bounds; loss within 2e-3;
+      ``mask_forms``: the crossatt_mask without text position 0 unmasked (fully masked query rows at every padded position)
+      gives finite gradients equal to the reference form's.
+    The batch run must take the production forms (recorded calls of the C library): the segment-parallel K2 with the policy's
+    segments for b x 4 heads and the full-head K2b (bf16), K14's cross-entropy, the training attention's fast form with per-row
+    text keys / values next to the shared positional table."""
+    from lina_speech_amd import blind_attention, ops
+    from lina_speech_amd.configs import l169
+    from kernel_cases import _FWD_SEG_NSEG, LibCalls, record_parity
+    torch.manual_seed(0)
+    model = reseed_parameters(l169(n_layer=1, txt_layers=1), seed=3).to(dev).train()
+    batch = collate_like_reference(padded_rows(b))
+    assert batch[1].shape[1] == max(PADDED_CODE_LENS[:b]) and batch[0].shape[1] == max(PADDED_TEXT_LENS[:b])
+    tag = f"padded batch b={b} vs its rows at b=1 ({str(dtype)[6:]})"
+
+    att_kv = []
+    orig_apply = blind_attention._TrainAttentionFunction.apply
+
+    def rec_apply(q, k, v, mask):
+        att_kv.append((q.shape[0], k.shape[0], v.shape[0]))
+        return orig_apply(q, k, v, mask)
+
+    blind_attention._TrainAttentionFunction.apply = rec_apply
+    try:
+        with LibCalls() as calls:
+            loss_b, grads_b = _train_grads(model, tuple(t.to(dev) for t in batch), dtype)
+    finally:
+        blind_attention._TrainAttentionFunction.apply = orig_apply
+    assert calls.of("lina_cross_entropy"), "the loss did not run on K14"
+    assert (b, b, 1) in att_kv and (b, 1, b) in att_kv, f"training attention forms: {att_kv}"
+    if dtype == torch.bfloat16:
+        want = ops.chunk_segments(b * 4, batch[1].shape[1] - 1)
+        segs = [int(a[_FWD_SEG_NSEG]) for a in calls.of("lina_gla_chunk_fwd_seg")]
+        assert want > 1 and segs and set(segs) == {want}, f"segment-parallel K2 launches {segs}, expected nseg={want}"
+        assert calls.of("lina_gla_chunk_bwd_full"), "K2b did not run on the full-head kernel"
+
+    counts, rows32 = _rows_alone(model, batch, dev, torch.float32)
+    loss_r, grads_r = _weighted(counts, rows32)
+    if dtype == torch.float32:
+        e_loss = abs(loss_b - loss_r) / abs(loss_r)
+        record_parity(f"{tag}: loss", e_loss, rel_loss)
+        assert e_loss <= rel_loss, (loss_b, loss_r)
+        errs, zeros = _max_rel_errors(grads_b, grads_r, 1e-5)
+        assert len(errs) > 80
+        worst = max(errs, key=errs.get)
+        record_parity(f"{tag}: worst per-tensor max|batch - rows| / max|rows| over {len(errs)} gradient tensors", errs[worst],
+                      rel_grad, tensor=worst, analytically_zero=len(zeros))
+        assert errs[worst] <= rel_grad, (worst, errs[worst])
+        # negative controls: a batching error of either kind (row 1 -- 2730 targets -- left out; every row weighted alike) lands
+        # far outside the bound
+        for what, override in (("row dropped", {1: 0}), ("rows weighted equally", {i: 1 for i in range(b)})):
+            _, g_bad = _weighted(counts, rows32, override)
+            e_bad = max(_max_rel_errors(grads_b, g_bad, 1.0)[0].values())
+            record_parity(f"{tag}: negative control ({what}) -- must exceed the bound", e_bad, rel_grad)
+            assert e_bad > 10 * rel_grad, f"negative control '{what}' passed the check ({e_bad:.2e}): the check does not bite"
+        if mask_forms:
+            nb = collate_like_reference(padded_rows(b), all_false_rows=True)
+            assert (~nb[3][:, :-1].any(-1)).any(), "the variant has no fully masked query row"
+            loss_n, grads_n = _train_grads(model, tuple(t.to(dev) for t in nb), dtype)
+            e_n = abs(loss_n - loss_b) / abs(loss_b)
+            errs_n, _ = _max_rel_errors(grads_n, {k: v.double() for k, v in grads_b.items()}, 1e-5)
+            worst_n = max(errs_n, key=errs_n.get)
+            record_parity(f"{tag}: crossatt_mask without position 0 unmasked vs with it, worst gradient", errs_n[worst_n],
+                          rel_grad, tensor=worst_n, loss_error=e_n)
+            assert e_n <= rel_loss and errs_n[worst_n] <= rel_grad, (e_n, worst_n, errs_n[worst_n])
+        return
+    _, rows16 = _rows_alone(model, batch, dev, torch.bfloat16)
+    loss_r16, grads_r16 = _weighted(counts, rows16)
+    e_loss = abs(loss_b - loss_r) / abs(loss_r)
+    record_parity(f"{tag}: loss vs the fp32 rows", e_loss, 2e-3, rows_bf16_loss_error=abs(loss_r16 - loss_r) / abs(loss_r))
+    assert e_loss <= 2e-3, (loss_b, loss_r)
+    largest = max(float(r.abs().max()) for r in grads_r.values())
+
+    def gaps(batch_grads):
+        """Per tensor (rows' cosine - batch's, batch's norm error - rows', name, cosines, norm errors), both against the fp32
+        rows; analytically-zero tensors skipped (noise on every side: a cosine means nothing)."""
+        out = []
+        for name, r in grads_r.items():
+            if float(r.abs().max()) < 1e-5 * largest:
+                continue
+            r = r.flatten()
+            res = []
+            for g in (batch_grads[name], grads_r16[name]):
+                g = g.double().flatten()
+                assert torch.isfinite(g).all(), name
+                res.append((float(g @ r / (g.norm() * r.norm()).clamp_min(1e-300)),
+                            abs(float(g.norm() - r.norm())) / float(r.norm())))
+            (cb, eb), (cr, er) = res
+            out.append((cr - cb, eb - er, name, (cb, cr), (eb, er)))
+        return out
+
+    def verdict(gs):
+        med_c, med_n = float(torch.tensor([t[0] for t in gs]).median()), float(torch.tensor([t[1] for t in gs]).median())
+        wc, wn = max(gs, key=lambda t: t[0]), max(gs, key=lambda t: t[1])
+        return wc, wn, med_c, med_n, (wc[0] <= max_cos_gap and wn[1] <= max_norm_gap and med_c <= med_cos_gap
+                                      and med_n <= med_norm_gap)
+
+    gs = gaps(grads_b)
+    assert len(gs) > 80
+    wc, wn, med_c, med_n, ok = verdict(gs)
+    record_parity(f"{tag}: largest (rows' cosine - batch's cosine) with the fp32 rows over {len(gs)} gradient tensors", wc[0],
+                  max_cos_gap, tensor=wc[2], batch_and_rows_cosine=wc[3], lowest_batch_cosine=min(t[3][0] for t in gs),
+                  median_gap=med_c, median_tolerance=med_cos_gap)
+    record_parity(f"{tag}: largest (batch's norm error - rows' norm error) vs the fp32 rows", wn[1], max_norm_gap, tensor=wn[2],
+                  batch_and_rows_norm_error=wn[4], largest_batch_norm_error=max(t[4][0] for t in gs), median_gap=med_n,
+                  median_tolerance=med_norm_gap)
+    assert ok, (wc, wn, med_c, med_n)
+    # negative control: the bf16 rows combined with every row weighted alike in place of the batch must fail these bounds
+    bad = verdict(gaps(_weighted(counts, rows16, {i: 1 for i in range(b)})[1]))
+    record_parity(f"{tag}: negative control (rows weighted equally): largest cosine gap -- must exceed the bound", bad[0][0],
+                  max_cos_gap, largest_norm_gap=bad[1][1], median_cosine_gap=bad[2], median_norm_gap=bad[3])
+    assert not bad[4], "negative control passed the bf16 check: the check does not bite"

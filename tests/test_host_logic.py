@@ -278,3 +278,12 @@ def test_host_paths_of_the_late_round6_train_ops_fall_back_to_torch():
     a = train_attention(q, k, v, mask)
     r = torch.nn.functional.scaled_dot_product_attention(q, k.expand(2, -1, -1, -1), v, attn_mask=mask)
     assert torch.allclose(a, r, rtol=1e-5, atol=1e-6)
+
+
+def test_train_attention_zeroes_fully_masked_rows_like_sdpa():
+    """A padded batch whose crossatt_mask is x_mask (x) y_mask WITHOUT the reference collate's unmasked text position 0 has
+    query rows with nothing to attend: ``train_attention`` gives 0 there and finite gradients, as
+    ``F.scaled_dot_product_attention`` does (before: NaN rows whose backward made every shared-operand gradient NaN) --
+    forward and the gradients of q, k, v, k / v with batch 1 and with batch B, fp32 (vs fp64) and bf16."""
+    from kernel_cases import check_train_attention_masked_rows
+    check_train_attention_masked_rows("cpu")

@@ -149,6 +149,15 @@ def test_chunk_segment_parallel(emu, T, nseg, resets):
     check_chunk_segmented(DEV, B=1, H=1, T=T, nseg=nseg, resets=resets)
 
 
+# B > 1 with different reset positions per batch row (make_gla_inputs resets="rows": resets straddling the segment boundaries,
+# a whole segment of cut-forcing gates, a row without resets): a slot-indexing error in the batch term of the segment-parallel
+# kernel shows in one row's output or final state.  T = 100 / nseg = 4: four 32-token segments, the last of 4 tokens;
+# T = 140 / nseg = 3: three 64-token segments, the last of 12.
+@pytest.mark.parametrize("T,nseg", [(100, 4), (140, 3)])
+def test_chunk_segment_parallel_batch_rows_with_their_own_resets(emu, T, nseg):
+    check_chunk_segmented(DEV, B=3, H=2, T=T, nseg=nseg, resets="rows")
+
+
 @pytest.mark.parametrize("C,dtype,ada", [(64, torch.float32, False), (768, torch.float32, True), (96, torch.bfloat16, True)])
 def test_dwconv7_ln(emu, C, dtype, ada):
     from kernel_cases import check_dwconv7_ln
@@ -343,6 +352,13 @@ def test_chunk_bwd_full_head_sweeps_edge_lengths(emu, T, nseg):
 @pytest.mark.parametrize("D,H,T,nseg", [(128, 2, 70, 1), (64, 4, 70, 2), (128, 4, 65, 2)])
 def test_chunk_bwd_full_head_sweeps_head_groups(emu, D, H, T, nseg):
     check_chunk_bwd_full(DEV, 1, H, T, D, nseg, resets=True)
+
+
+@pytest.mark.parametrize("T,nseg,via_autograd", [(100, 4, True), (140, 3, False)])
+def test_chunk_bwd_full_head_sweeps_batch_rows_with_their_own_resets(emu, T, nseg, via_autograd):
+    # the backward's mirror of the case above, called directly and (T = 100) through chunk_gla autograd as well: the forward's
+    # segment start states handed over, the gradients equal to the oracle's and to the nseg = 1 single pass
+    check_chunk_bwd_full(DEV, 3, 2, T, 256, nseg, resets="rows", via_autograd=via_autograd)
 
 
 def test_chunk_bwd_generic_kernel_still_reachable_for_bf16(emu, monkeypatch):

@@ -315,6 +315,28 @@ def test_chunk_segment_parallel_at_the_training_sequence_length(hip, nseg, reset
     check_chunk_segmented(DEV, B=1, H=4, T=4096, nseg=nseg, resets=resets)
 
 
+# B > 1 at the training length, per-row reset positions (make_gla_inputs resets="rows": resets straddling the segment
+# boundaries, a whole segment of cut-forcing gates, rows without resets), every row's output and final state vs the fp64
+# oracle.  The policy's own choices at config 5's micro-batches: b = 8 -> 8 segments, b = 16 -> 4; then a ragged tail with
+# forced segments and, at T = 257 with 16 segments asked for, empty trailing segments.
+@pytest.mark.parametrize("B,T,nseg,expect", [(8, 4096, None, 8), (16, 4096, None, 4), (3, 4096 - 37, 8, None),
+                                             (2, 257, 16, None)])
+def test_chunk_segment_parallel_batch_rows_with_their_own_resets(hip, B, T, nseg, expect):
+    check_chunk_segmented(DEV, B=B, H=4, T=T, nseg=nseg, resets="rows", expect_nseg=expect)
+
+
+def test_chunk_bwd_full_batch_rows_at_the_training_length_and_the_segment_state_handoff(hip):
+    """K2b at config 5's micro-batch shape (B = 8, H = 4, T = 4096, 8 segments) with per-row resets, called directly and
+    through ops.chunk_gla autograd (the forward's segment start states handed to K2b), against the fp64 oracle gradients,
+    row by row, and the autograd gradients against the nseg = 1 single pass."""
+    check_chunk_bwd_full(DEV, 8, 4, 4096, 256, 8, resets="rows", via_autograd=True)
+
+
+def test_train_attention_zeroes_fully_masked_rows_like_sdpa(hip):
+    from kernel_cases import check_train_attention_masked_rows
+    check_train_attention_masked_rows(DEV, T=300, S=40, d=1024)
+
+
 # ----------------------------------------------------------------------------- K1w: windowed decode-step update
 @pytest.mark.parametrize("B,H,Dk,Dv,dtype,window,n", [(64, 4, 256, 256, torch.bfloat16, 8, 21), (3, 2, 256, 256, torch.float32, 8, 17),
                                                       (5, 8, 128, 128, torch.bfloat16, 4, 10), (2, 16, 64, 64, torch.float32, 8, 9),

@@ -477,6 +477,24 @@ def test_config5_slice_at_sequence_length_4096_bf16_autocast_tracks_reference_au
     check_config5_slice_golden("cuda", torch.bfloat16, rel_loss=5e-3)
 
 
+def test_config5_slice_padded_batch_of_8_equals_its_rows_fp32(hip):
+    """The train step on a padded b = 8 batch (ragged code lengths up to 4097, ragged text, the reference collate's masks) equals
+    its rows run alone at b = 1 -- the path the T = 4096 goldens pin to the reference's autograd -- combined by their counted
+    targets: loss within 1e-5 and every parameter gradient within 1e-3 (negative controls must fail that bound); and the crossatt_mask
+    without text position 0 unmasked gives the same finite gradients."""
+    from model_cases import check_padded_batch_equals_rows
+    check_padded_batch_equals_rows("cuda", b=8, dtype=torch.float32)
+
+
+@pytest.mark.parametrize("b", [8, 16])
+def test_config5_slice_padded_batch_equals_its_rows_bf16_autocast(hip, b):
+    """The same under bf16 autocast (the way training runs; b = 8: 8 segments, b = 16: 4): the batch is as close to the fp32 rows
+    as the bf16 rows are (per-tensor cosine and norm error, worst case and median: see check_padded_batch_equals_rows) and the
+    loss within 2e-3."""
+    from model_cases import check_padded_batch_equals_rows
+    check_padded_batch_equals_rows("cuda", b=b, dtype=torch.bfloat16)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_config5_slice_bigram_targets_cosine_with_reference_gradients(hip, dtype):
     """A bf16 train check that bites: the T = 4096 slice on coherent (bigram) targets -- fp32 entries within
