@@ -552,6 +552,29 @@ int lina_softmax_rows(const void* x, int64_t x_sb, int x_dtype, float scale, voi
 int lina_weighted_rows_add(const void* attc, int Tp, const void* vv, void* x, int B, int T_txt, int d,
                            int dtype, lina_stream_t stream);
 
+/* Ragged text: the three launches of the default cross-attention step for a batch of right-padded texts of different
+ * lengths.  txt_len: int32 [B] on the device, row b's text length L_b (1 <= L_b <= T_txt; a value outside is clamped to that
+ * range).  T_txt stays the row stride of kk / vv / scores and the width of the att rows; positions t >= L_b are left out by
+ * the loop bounds (row b's sums are the instructions of a launch with T_txt = L_b, and kk / vv rows t >= L_b are not read).
+ *   lina_cross_scores_ragged               : lina_cross_scores for t < L_b (scores[b, L_b:] not written);
+ *   lina_softmax_pe_rows_ragged            : lina_softmax_pe_rows over [0, L_b) with row b's table at pe + b*pe_sb
+ *                                            (pe_sb = 0: one shared [T_txt, d] table); att rows get zeros on [L_b, T_txt);
+ *   lina_pe_softmax_weighted_rows_add_ragged: lina_pe_softmax_weighted_rows_add over [0, L_b), the same per-row table and
+ *                                            zeroed att tail, for any d % 4 == 0 (d <= 8192; packed operands: whole k-steps).
+ * The att-log arguments are those of lina_softmax_pe_rows. */
+int lina_cross_scores_ragged(const void* q_lin, const void* ln_w, const void* ln_b, float ln_eps, const void* kk,
+                             float* scores, const int32_t* txt_len, int B, int T_txt, int d, float scale, int dtype,
+                             lina_stream_t stream);
+int lina_softmax_pe_rows_ragged(const float* scores, int64_t scores_sb, void* att, int64_t att_sb,
+                                const int64_t* att_step, int64_t att_step_stride, int64_t att_steps,
+                                const void* pe, int64_t pe_sb, const int32_t* txt_len, void* xp,
+                                void* xp_packed, int B, int T_txt, int d, int dtype, lina_stream_t stream);
+int lina_pe_softmax_weighted_rows_add_ragged(const void* xp, int xp_packed, const void* pe, int64_t pe_sb,
+                                             const int32_t* txt_len, float scale, void* att, int64_t att_sb,
+                                             const int64_t* att_step, int64_t att_step_stride, int64_t att_steps,
+                                             const void* vv, void* x, void* x_packed, int B, int T_txt, int d,
+                                             int dtype, lina_stream_t stream);
+
 /* ---- f-3: the codes -> waveform step after the generation path (reference 3rdparty/decoder) ---- */
 
 /* K8 -- depthwise conv (kernel 7, "same" zero padding along L) fused with the LayerNorm / AdaLayerNorm over C

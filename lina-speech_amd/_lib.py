@@ -92,6 +92,10 @@ PROTOTYPES = {
     "lina_pe_softmax_weighted_rows_add": (C.c_int, [_p, _i, _p, _f, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i, _i, _i, _i, _p]),
     "lina_softmax_pe_rows": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i, _i, _i, _i, _p]),
     "lina_cross_scores": (C.c_int, [_p, _p, _p, _f, _p, _p, _i, _i, _i, _f, _i, _p]),
+    "lina_cross_scores_ragged": (C.c_int, [_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _f, _i, _p]),
+    "lina_softmax_pe_rows_ragged": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "lina_pe_softmax_weighted_rows_add_ragged": (C.c_int, [_p, _i, _p, _i64, _p, _f, _p, _i64, _p, _i64, _i64, _p, _p, _p,
+                                                           _i, _i, _i, _i, _p]),
     "lina_softmax_rows": (C.c_int, [_p, _i64, _i, _f, _p, _i64, _p, _i, _i, _i, _i, _p]),
     "lina_weighted_rows_add": (C.c_int, [_p, _i, _p, _p, _i, _i, _i, _i, _p]),
     "lina_gla_decode_inproj": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,

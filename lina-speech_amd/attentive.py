@@ -122,11 +122,13 @@ class AttentiveGLA(AttentiveRNN):
         self.cross_att.pos_net.mode = mode  # attribute on the block, exactly as the reference sets it (gla.py:333)
 
     # single-token decode
-    def step(self, y_embd, x_enc, time_step, cache, prepared=None):
+    def step(self, y_embd, x_enc, time_step, cache, prepared=None, crossatt_mask=None):
+        """``crossatt_mask`` [B, T, Ttxt] bool (right-padded texts: True on each row's text), with ``prepared`` from
+        ``cross_att.prepare(x_enc, lens=...)`` -- the per-row positional tables the mask belongs to."""
         kw = dict(past_key_values=cache, use_cache=True)
         for blk in self.encoder:
             y_embd = blk(y_embd, **kw)
-        v, att = self.cross_att(y_embd, x_enc, time_step=time_step, prepared=prepared, **kw)
+        v, att = self.cross_att(y_embd, x_enc, mask=crossatt_mask, time_step=time_step, prepared=prepared, **kw)
         y_embd = y_embd + v
         for blk in self.decoder:
             y_embd = blk(y_embd, **kw)

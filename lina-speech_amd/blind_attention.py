@@ -170,13 +170,30 @@ class BlindCrossAttention(nn.Module):
             return ops.layer_norm(x, ln.weight, ln.bias, ln.eps)
         return ln(x)
 
-    def prepare(self, ctx, pos=None):
-        """Step-invariant text side: (k, v, pos_emb), each [B|1, 1, Ttxt, d]."""
+    def prepare(self, ctx, pos=None, lens=None):
+        """Step-invariant text side: (k, v, pos_emb), each [B|1, 1, Ttxt, d].  ``lens`` [B] (decoding right-padded texts of
+        these lengths): the positional table of every row at its OWN text width, zero past it -- [B, 1, Ttxt, d] for ConvPos
+        (a 'same' convolution of kernel 31: a row's last 15 positions depend on the width; with the embedding rows >= L_b
+        zeroed before it the convolution equals the one at width L_b), the shared table for the pointwise SinPos."""
         k = self._norm(self.ln_k, ops.linear(ctx, self.k.weight, self.k.bias)).unsqueeze(1)   # (ops.linear: nn.Linear's forward;
         v = self._norm(self.ln_v, ops.linear(ctx, self.v.weight, self.v.bias)).unsqueeze(1)   #  bias gradient as K13a / K13)
         if pos is None:
             pos = torch.arange(ctx.shape[1], device=ctx.device).unsqueeze(0)
-        return k, v, self.pos_embed(pos).unsqueeze(1)
+        if lens is None or not self.per_row_table:
+            return k, v, self.pos_embed(pos).unsqueeze(1)
+        return k, v, self.pos_table_rows(pos, lens).unsqueeze(1)
+
+    @property
+    def per_row_table(self) -> bool:
+        """Ragged text: does a row's positional table depend on its text width (ConvPos) or not (the pointwise SinPos)?"""
+        return isinstance(self.pos_embed, ConvPos)
+
+    def pos_table_rows(self, pos, lens):
+        """The ConvPos table of every row at its own text width ``lens[b]``: [B, Ttxt, d], zero past it -- the embedding rows
+        >= L_b zeroed before the convolution, which then equals the one at width L_b."""
+        pad = (torch.arange(pos.shape[-1], device=pos.device)[None, :] >= lens.to(pos.device)[:, None]).unsqueeze(-1)
+        e = self.pos_embed.embed(pos).expand(lens.shape[0], -1, -1).masked_fill(pad, 0.0)
+        return self.pos_embed.dw_conv(e.transpose(1, 2)).transpose(1, 2).masked_fill(pad, 0.0)
 
     def forward(self, q, k, mask=None, time_step=None, pos=None, prepared=None, **kwargs):
         kk, vv, pe = prepared if prepared is not None else self.prepare(k, pos)

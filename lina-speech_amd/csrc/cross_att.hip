@@ -72,14 +72,18 @@ __device__ unsigned long long lina_cross_prof[1024 * 8];
 #endif
 
 // scores[b,t] = scale * <LN(q_lin[b]), kk[b,t,:]>   grid (ceil(Tn/16), B): 4 waves x 4 text rows each
-template <typename T>
-__global__ __launch_bounds__(256) void cross_scores_kernel(
+// kRagged (lina_cross_scores_ragged): row b's text ends at Tl = txt_len[b]; only t < Tl is scored (Tn stays the row stride
+// of kk and scores), the workgroups past Tl leave at once and no text row at or beyond Tl is read
+template <typename T, bool kRagged>
+__device__ __forceinline__ void cross_scores_body(
     const T* __restrict__ qlin, const T* __restrict__ ln_w, const T* __restrict__ ln_b, float ln_eps,
-    const T* __restrict__ kk, float* __restrict__ scores, int Tn, int d, float scale) {
+    const T* __restrict__ kk, float* __restrict__ scores, int Tn, int d, float scale, const int32_t* __restrict__ txt_len) {
     LINA_DYN_SMEM(smem);
     float* s_q = reinterpret_cast<float*>(smem);            // [d]
     __shared__ float s_red[4];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int Tl = kRagged ? min(max(txt_len[b], 1), Tn) : Tn;   // (clamped: a bad length cannot leave the row)
+    if (kRagged && (int)blockIdx.x * 16 >= Tl) return;      // workgroup-uniform, before any barrier
 #ifdef LINA_SKINNY_PROF
     unsigned long long pr_[8] = {};
     CS_PROF(0, wall_clock64());
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(256) void cross_scores_kernel(
     float4 m[4][kIt];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int t = min((int)blockIdx.x * 16 + 4 * w + i, Tn - 1);
+        const int t = min((int)blockIdx.x * 16 + 4 * w + i, Tl - 1);
         const T* row = kk + ((int64_t)b * Tn + t) * d;
 #pragma unroll
         for (int it = 0; it < kIt; ++it) {
@@ -158,7 +162,7 @@ __global__ __launch_bounds__(256) void cross_scores_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int t = blockIdx.x * 16 + 4 * w + i;           // wave-uniform
-        if (t >= Tn) break;
+        if (t >= Tl) break;
         float acc = 0.0f;
         if (pre) {
 #pragma unroll
@@ -190,6 +194,18 @@ __global__ __launch_bounds__(256) void cross_scores_kernel(
             for (int i = 0; i < 8; ++i) lina_cross_prof[wg * 8 + i] = pr_[i];
     }
 #endif
+}
+template <typename T>
+__global__ __launch_bounds__(256) void cross_scores_kernel(
+    const T* __restrict__ qlin, const T* __restrict__ ln_w, const T* __restrict__ ln_b, float ln_eps,
+    const T* __restrict__ kk, float* __restrict__ scores, int Tn, int d, float scale) {
+    cross_scores_body<T, false>(qlin, ln_w, ln_b, ln_eps, kk, scores, Tn, d, scale, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void cross_scores_ragged_kernel(
+    const T* __restrict__ qlin, const T* __restrict__ ln_w, const T* __restrict__ ln_b, float ln_eps,
+    const T* __restrict__ kk, float* __restrict__ scores, int Tn, int d, float scale, const int32_t* __restrict__ txt_len) {
+    cross_scores_body<T, true>(qlin, ln_w, ln_b, ln_eps, kk, scores, Tn, d, scale, txt_len);
 }
 
 // row softmax of x[b, 0:Tn] * scale; written (model dtype) to the strided attention buffer AND to a contiguous
@@ -423,33 +439,40 @@ __global__ __launch_bounds__(256) void softmax_weighted_rows_kernel(const T* __r
 //                                            projection GEMM this replaces stored them)
 // itself -- T_txt x d multiply-adds per workgroup (65 k at L169: nothing), pe's T_txt rows come from L2 (shared by every
 // workgroup) -- instead of a launch of its own that 256 CUs wait for.  xp is read row-major or fragment-major (xp_packed).
-template <typename T>
-__global__ __launch_bounds__(256) void pe_softmax_weighted_rows_kernel(const T* __restrict__ xp, int xp_packed,
-                                                                       const T* __restrict__ pe, float scale,
-                                                                       T* __restrict__ att, int64_t att_sb,
-                                                                       const T* __restrict__ vv, T* x, int Tn, int d, T* xpk,
-                                                                       const int64_t* __restrict__ att_step, int64_t att_ss,
-                                                                       int64_t att_ns) {
+// kRagged (lina_pe_softmax_weighted_rows_add_ragged): row b's text ends at Tl = txt_len[b] -- scores, softmax and att2 . V
+// over t < Tl only (Tn stays the row stride of vv and the width of the att row, written with zeros on [Tl, Tn)), the table
+// of row b at pe + b * pe_sb (0: shared), and any d % 4 == 0 (the lanes past d of the last 256-column piece stay idle)
+template <typename T, bool kRagged>
+__device__ __forceinline__ void pe_softmax_weighted_rows_body(const T* __restrict__ xp, int xp_packed,
+                                                              const T* __restrict__ pe, float scale,
+                                                              T* __restrict__ att, int64_t att_sb,
+                                                              const T* __restrict__ vv, T* x, int Tn, int d, T* xpk,
+                                                              const int64_t* __restrict__ att_step, int64_t att_ss,
+                                                              int64_t att_ns, int64_t pe_sb,
+                                                              const int32_t* __restrict__ txt_len) {
     LINA_DYN_SMEM(smem);
     float* s_x = reinterpret_cast<float*>(smem);              // [d]: the row of x_pos in fp32
     __shared__ float s_a[kCaMaxT];
     __shared__ float s_red[4];
     __shared__ __attribute__((aligned(16))) float s_p[3][64][4];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int Tl = kRagged ? min(max(txt_len[b], 1), Tn) : Tn;
+    const T* peb = kRagged ? pe + (int64_t)b * pe_sb : pe;
     for (int e = 4 * tid; e < d; e += 1024) {
         const float4 v4 = ld4(xp_packed ? xp + packed_off<T>(b, e, d) : xp + (int64_t)b * d + e);
         *reinterpret_cast<float4*>(&s_x[e]) = v4;
     }
     __syncthreads();
     // wave w takes the text positions w, w+4, ...: a lane covers the columns 4 lane + 256 c; four positions in flight
-    const int nc = d / 256;                                   // (launcher: d % 256 == 0)
-    for (int t0 = w; t0 < Tn; t0 += 16) {
+    const int nc = kRagged ? (d + 255) / 256 : d / 256;       // (uniform launcher: d % 256 == 0)
+    for (int t0 = w; t0 < Tl; t0 += 16) {
         float part[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int t = min(t0 + 4 * u, Tn - 1);
-            const T* row = pe + (int64_t)t * d + 4 * lane;
+            const int t = min(t0 + 4 * u, Tl - 1);
+            const T* row = peb + (int64_t)t * d + 4 * lane;
             for (int c = 0; c < nc; ++c) {
+                if (kRagged && 4 * lane + 256 * c >= d) break;
                 const float4 pv = ld4(row + 256 * c);
                 const float4 xv = *reinterpret_cast<const float4*>(&s_x[4 * lane + 256 * c]);
                 part[u] = fmaf(pv.x, xv.x, part[u]); part[u] = fmaf(pv.y, xv.y, part[u]);
@@ -461,7 +484,7 @@ __global__ __launch_bounds__(256) void pe_softmax_weighted_rows_kernel(const T* 
             float a = part[u];
             a += shfl_xor(a, 1); a += shfl_xor(a, 2); a += shfl_xor(a, 4);
             a += shfl_xor(a, 8); a += shfl_xor(a, 16); a += shfl_xor(a, 32);
-            if (lane == 0 && t0 + 4 * u < Tn) {
+            if (lane == 0 && t0 + 4 * u < Tl) {
                 T tmp;                                        // the projection's output dtype
                 st(&tmp, a);
                 s_a[t0 + 4 * u] = ld(&tmp) * scale;
@@ -470,21 +493,23 @@ __global__ __launch_bounds__(256) void pe_softmax_weighted_rows_kernel(const T* 
     }
     __syncthreads();
     float mx = -INFINITY;
-    for (int t = tid; t < Tn; t += 256) mx = fmaxf(mx, s_a[t]);
+    for (int t = tid; t < Tl; t += 256) mx = fmaxf(mx, s_a[t]);
     mx = block_max(mx, s_red);
     float sum = 0.0f;
-    for (int t = tid; t < Tn; t += 256) sum += expf(s_a[t] - mx);
+    for (int t = tid; t < Tl; t += 256) sum += expf(s_a[t] - mx);
     sum = block_sum(sum, s_red);
     const float inv = 1.0f / sum;
     // att log of the device-side decode loop: the row goes to att + step[0] * att_ss (dropped outside [0, att_ns))
     const int64_t a_t = att_step ? att_step[0] : 0;
     const bool a_ok = blockIdx.x == 0 && (!att_step || (a_t >= 0 && a_t < att_ns));
-    for (int t = tid; t < Tn; t += 256) {
+    for (int t = tid; t < Tl; t += 256) {
         T tmp;                                               // the weights in the model dtype, as softmax_rows stores them
         st(&tmp, expf(s_a[t] - mx) * inv);
         s_a[t] = ld(&tmp);
         if (a_ok) att[b * att_sb + a_t * att_ss + t] = tmp;
     }
+    if (kRagged && a_ok)                                     // the att buffers are reused: the text's padding gets zeros
+        for (int t = Tl + tid; t < Tn; t += 256) st(att + b * att_sb + a_t * att_ss + t, 0.0f);
     __syncthreads();
     // the row's 256-column slabs: one per workgroup (grid.x = d / 256: small batches, more workgroups) or all of them in turn
     // (grid.x = 1: at B >= 256 the T_txt x d scores above -- pe's 128 KB from L2 and 65 k multiply-adds per workgroup -- were
@@ -495,13 +520,13 @@ __global__ __launch_bounds__(256) void pe_softmax_weighted_rows_kernel(const T* 
         const bool live = e < d;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         const T* base = vv + (int64_t)b * Tn * d + (live ? e : 0);
-        for (int t0 = w; t0 < Tn; t0 += 32) {
+        for (int t0 = w; t0 < Tl; t0 += 32) {
             float4 p[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) p[u] = ld4(base + (int64_t)min(t0 + 4 * u, Tn - 1) * d);
+            for (int u = 0; u < 8; ++u) p[u] = ld4(base + (int64_t)min(t0 + 4 * u, Tl - 1) * d);
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const float a = (t0 + 4 * u < Tn) ? s_a[min(t0 + 4 * u, Tn - 1)] : 0.0f;
+                const float a = (t0 + 4 * u < Tl) ? s_a[min(t0 + 4 * u, Tl - 1)] : 0.0f;
                 acc.x = fmaf(a, p[u].x, acc.x); acc.y = fmaf(a, p[u].y, acc.y);
                 acc.z = fmaf(a, p[u].z, acc.z); acc.w = fmaf(a, p[u].w, acc.w);
             }
@@ -523,6 +548,27 @@ __global__ __launch_bounds__(256) void pe_softmax_weighted_rows_kernel(const T* 
         __syncthreads();                                      // the partial sums have been read: the next slab may write them
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void pe_softmax_weighted_rows_kernel(const T* __restrict__ xp, int xp_packed,
+                                                                       const T* __restrict__ pe, float scale,
+                                                                       T* __restrict__ att, int64_t att_sb,
+                                                                       const T* __restrict__ vv, T* x, int Tn, int d, T* xpk,
+                                                                       const int64_t* __restrict__ att_step, int64_t att_ss,
+                                                                       int64_t att_ns) {
+    pe_softmax_weighted_rows_body<T, false>(xp, xp_packed, pe, scale, att, att_sb, vv, x, Tn, d, xpk, att_step, att_ss,
+                                            att_ns, 0, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void pe_softmax_weighted_rows_ragged_kernel(const T* __restrict__ xp, int xp_packed,
+                                                                              const T* __restrict__ pe, int64_t pe_sb,
+                                                                              const int32_t* __restrict__ txt_len, float scale,
+                                                                              T* __restrict__ att, int64_t att_sb,
+                                                                              const T* __restrict__ vv, T* x, int Tn, int d,
+                                                                              T* xpk, const int64_t* __restrict__ att_step,
+                                                                              int64_t att_ss, int64_t att_ns) {
+    pe_softmax_weighted_rows_body<T, true>(xp, xp_packed, pe, scale, att, att_sb, vv, x, Tn, d, xpk, att_step, att_ss,
+                                           att_ns, pe_sb, txt_len);
+}
 
 // softmax + att . pe in ONE launch (the first half of the blind cross-attention, reference model/crossatt.py:117-127):
 //   att[b, :Tn] = softmax(scores[b, :Tn])  (scores: fp32, already scaled -- lina_cross_scores' output);
@@ -531,49 +577,54 @@ __global__ __launch_bounds__(256) void pe_softmax_weighted_rows_kernel(const T* 
 // grid (ceil(d / 256), B) like softmax_weighted_rows_kernel: with lina_cross_scores in front (256 workgroups on the text
 // keys) this replaces {scores + softmax in ONE 1024-thread workgroup per row, then a K = T_txt skinny GEMM}: the row-wide
 // workgroups of that form put 64 CUs on 8.4 MB of HBM-cold keys (11.5 us per launch in the step's timeline).
-template <typename T>
-__global__ __launch_bounds__(256) void softmax_pe_rows_kernel(const float* __restrict__ scores, int64_t sc_sb,
-                                                              T* __restrict__ att, int64_t att_sb, const T* __restrict__ pe,
-                                                              T* __restrict__ xp, T* __restrict__ xpk, int Tn, int d,
-                                                              const int64_t* __restrict__ att_step, int64_t att_ss,
-                                                              int64_t att_ns) {
+// kRagged (lina_softmax_pe_rows_ragged): row b's text ends at Tl = txt_len[b] -- softmax and att . pe over t < Tl only, the
+// table of row b at pe + b * pe_sb (0: shared); Tn stays the width of the att row, written with zeros on [Tl, Tn)
+template <typename T, bool kRagged>
+__device__ __forceinline__ void softmax_pe_rows_body(const float* __restrict__ scores, int64_t sc_sb,
+                                                     T* __restrict__ att, int64_t att_sb, const T* __restrict__ pe,
+                                                     T* __restrict__ xp, T* __restrict__ xpk, int Tn, int d,
+                                                     const int64_t* __restrict__ att_step, int64_t att_ss,
+                                                     int64_t att_ns, int64_t pe_sb, const int32_t* __restrict__ txt_len) {
     __shared__ float s_a[kCaMaxT];
     __shared__ float s_red[4];
     __shared__ __attribute__((aligned(16))) float s_p[3][64][4];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int e = blockIdx.x * 256 + lane * 4;
     const bool live = e < d;
+    const int Tl = kRagged ? min(max(txt_len[b], 1), Tn) : Tn;
     // the scores first (a wave's loads return in order), then the first pe rows of this wave: they do not depend on the softmax
-    const T* base = pe + (live ? e : 0);
-    const float sc0 = tid < Tn ? scores[b * sc_sb + tid] : -INFINITY;
+    const T* base = (kRagged ? pe + (int64_t)b * pe_sb : pe) + (live ? e : 0);
+    const float sc0 = tid < Tl ? scores[b * sc_sb + tid] : -INFINITY;
     float4 p0[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) p0[u] = ld4(base + (int64_t)min(w + 4 * u, Tn - 1) * d);
+    for (int u = 0; u < 8; ++u) p0[u] = ld4(base + (int64_t)min(w + 4 * u, Tl - 1) * d);
     float mx = -INFINITY;
-    for (int t = tid; t < Tn; t += 256) { const float v = t == tid ? sc0 : scores[b * sc_sb + t]; s_a[t] = v; mx = fmaxf(mx, v); }
+    for (int t = tid; t < Tl; t += 256) { const float v = t == tid ? sc0 : scores[b * sc_sb + t]; s_a[t] = v; mx = fmaxf(mx, v); }
     mx = block_max(mx, s_red);
     float sum = 0.0f;
-    for (int t = tid; t < Tn; t += 256) sum += expf(s_a[t] - mx);
+    for (int t = tid; t < Tl; t += 256) sum += expf(s_a[t] - mx);
     sum = block_sum(sum, s_red);
     const float inv = 1.0f / sum;
     // att log of the device-side decode loop: the row goes to att + step[0] * att_ss (dropped outside [0, att_ns))
     const int64_t a_t = att_step ? att_step[0] : 0;
     const bool a_ok = blockIdx.x == 0 && (!att_step || (a_t >= 0 && a_t < att_ns));
-    for (int t = tid; t < Tn; t += 256) {
+    for (int t = tid; t < Tl; t += 256) {
         T tmp;                                               // the weights in the model dtype, as softmax_rows stores them
         st(&tmp, expf(s_a[t] - mx) * inv);
         s_a[t] = ld(&tmp);
         if (a_ok) att[b * att_sb + a_t * att_ss + t] = tmp;
     }
+    if (kRagged && a_ok)                                     // the att buffers are reused: the text's padding gets zeros
+        for (int t = Tl + tid; t < Tn; t += 256) st(att + b * att_sb + a_t * att_ss + t, 0.0f);
     __syncthreads();
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t0 = w; t0 < Tn; t0 += 32) {
+    for (int t0 = w; t0 < Tl; t0 += 32) {
         float4 p[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) p[u] = t0 == w ? p0[u] : ld4(base + (int64_t)min(t0 + 4 * u, Tn - 1) * d);
+        for (int u = 0; u < 8; ++u) p[u] = t0 == w ? p0[u] : ld4(base + (int64_t)min(t0 + 4 * u, Tl - 1) * d);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            const float a = (t0 + 4 * u < Tn) ? s_a[min(t0 + 4 * u, Tn - 1)] : 0.0f;
+            const float a = (t0 + 4 * u < Tl) ? s_a[min(t0 + 4 * u, Tl - 1)] : 0.0f;
             acc.x = fmaf(a, p[u].x, acc.x); acc.y = fmaf(a, p[u].y, acc.y);
             acc.z = fmaf(a, p[u].z, acc.z); acc.w = fmaf(a, p[u].w, acc.w);
         }
@@ -592,6 +643,24 @@ __global__ __launch_bounds__(256) void softmax_pe_rows_kernel(const float* __res
         st4(tmp4, acc);
         st4(xpk + packed_off<T>(b, e, d), ld4(tmp4));
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_pe_rows_kernel(const float* __restrict__ scores, int64_t sc_sb,
+                                                              T* __restrict__ att, int64_t att_sb, const T* __restrict__ pe,
+                                                              T* __restrict__ xp, T* __restrict__ xpk, int Tn, int d,
+                                                              const int64_t* __restrict__ att_step, int64_t att_ss,
+                                                              int64_t att_ns) {
+    softmax_pe_rows_body<T, false>(scores, sc_sb, att, att_sb, pe, xp, xpk, Tn, d, att_step, att_ss, att_ns, 0, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_pe_rows_ragged_kernel(const float* __restrict__ scores, int64_t sc_sb,
+                                                                     T* __restrict__ att, int64_t att_sb,
+                                                                     const T* __restrict__ pe, int64_t pe_sb,
+                                                                     const int32_t* __restrict__ txt_len,
+                                                                     T* __restrict__ xp, T* __restrict__ xpk, int Tn, int d,
+                                                                     const int64_t* __restrict__ att_step, int64_t att_ss,
+                                                                     int64_t att_ns) {
+    softmax_pe_rows_body<T, true>(scores, sc_sb, att, att_sb, pe, xp, xpk, Tn, d, att_step, att_ss, att_ns, pe_sb, txt_len);
 }
 
 template <typename T>
@@ -853,6 +922,76 @@ extern "C" int lina_pe_softmax_weighted_rows_add(const void* xp, int xp_packed, 
                     (const bf16_t*)pe, scale, (bf16_t*)att, att_sb, (const bf16_t*)vv, (bf16_t*)x, Tn, d,
                     (bf16_t*)x_packed, att_step, att_step_stride, att_steps);
     return check_launch("lina_pe_softmax_weighted_rows_add");
+}
+
+// ---- ragged text (per-row lengths txt_len [B], int32, on the device): the kernels above with kRagged = true ------------
+extern "C" int lina_cross_scores_ragged(const void* q_lin, const void* ln_w, const void* ln_b, float ln_eps, const void* kk,
+                                        float* scores, const int32_t* txt_len, int B, int Tn, int d, float scale, int dtype,
+                                        lina_stream_t stream) {
+    using namespace lina;
+    LINA_REQUIRE(q_lin && ln_w && ln_b && kk && scores && txt_len, "lina_cross_scores_ragged: null pointer");
+    LINA_REQUIRE(B > 0 && Tn > 0, "lina_cross_scores_ragged: B, T_txt must be positive");
+    LINA_REQUIRE(d > 0 && d % 4 == 0 && d <= 16384, "lina_cross_scores_ragged: d must be a multiple of 4, <= 16384");
+    LINA_REQUIRE(valid_dtype(dtype), "lina_cross_scores_ragged: bad dtype %d", dtype);
+    dim3 grid((unsigned)((Tn + 15) / 16), (unsigned)B);
+    const size_t smem = sizeof(float) * (size_t)d;
+    if (dtype == LINA_F32)
+        LINA_LAUNCH((cross_scores_ragged_kernel<float>), grid, dim3(256), smem, stream, (const float*)q_lin,
+                    (const float*)ln_w, (const float*)ln_b, ln_eps, (const float*)kk, scores, Tn, d, scale, txt_len);
+    else
+        LINA_LAUNCH((cross_scores_ragged_kernel<bf16_t>), grid, dim3(256), smem, stream, (const bf16_t*)q_lin,
+                    (const bf16_t*)ln_w, (const bf16_t*)ln_b, ln_eps, (const bf16_t*)kk, scores, Tn, d, scale, txt_len);
+    return check_launch("lina_cross_scores_ragged");
+}
+
+extern "C" int lina_softmax_pe_rows_ragged(const float* scores, int64_t scores_sb, void* att, int64_t att_sb,
+                                           const int64_t* att_step, int64_t att_step_stride, int64_t att_steps,
+                                           const void* pe, int64_t pe_sb, const int32_t* txt_len, void* xp,
+                                           void* xp_packed, int B, int Tn, int d, int dtype, lina_stream_t stream) {
+    using namespace lina;
+    LINA_REQUIRE(scores && att && pe && xp && txt_len, "lina_softmax_pe_rows_ragged: null pointer");
+    LINA_REQUIRE(B > 0 && Tn > 0 && Tn <= kCaMaxT, "lina_softmax_pe_rows_ragged: 0 < T_txt <= %d", kCaMaxT);
+    LINA_REQUIRE(d > 0 && d % 4 == 0, "lina_softmax_pe_rows_ragged: d must be a multiple of 4");
+    LINA_REQUIRE(pe_sb >= 0, "lina_softmax_pe_rows_ragged: negative table stride");
+    LINA_REQUIRE(valid_dtype(dtype), "lina_softmax_pe_rows_ragged: bad dtype %d", dtype);
+    LINA_REQUIRE(!xp_packed || d % (dtype == LINA_BF16 ? 32 : 16) == 0,
+                 "lina_softmax_pe_rows_ragged: packed copy needs whole k-steps");
+    dim3 grid((unsigned)((d + 255) / 256), (unsigned)B);
+    if (dtype == LINA_F32)
+        LINA_LAUNCH((softmax_pe_rows_ragged_kernel<float>), grid, dim3(256), 0, stream, scores, scores_sb, (float*)att, att_sb,
+                    (const float*)pe, pe_sb, txt_len, (float*)xp, (float*)xp_packed, Tn, d, att_step, att_step_stride,
+                    att_steps);
+    else
+        LINA_LAUNCH((softmax_pe_rows_ragged_kernel<bf16_t>), grid, dim3(256), 0, stream, scores, scores_sb, (bf16_t*)att,
+                    att_sb, (const bf16_t*)pe, pe_sb, txt_len, (bf16_t*)xp, (bf16_t*)xp_packed, Tn, d, att_step,
+                    att_step_stride, att_steps);
+    return check_launch("lina_softmax_pe_rows_ragged");
+}
+
+extern "C" int lina_pe_softmax_weighted_rows_add_ragged(const void* xp, int xp_packed, const void* pe, int64_t pe_sb,
+                                                        const int32_t* txt_len, float scale, void* att, int64_t att_sb,
+                                                        const int64_t* att_step, int64_t att_step_stride, int64_t att_steps,
+                                                        const void* vv, void* x, void* x_packed, int B, int Tn, int d,
+                                                        int dtype, lina_stream_t stream) {
+    using namespace lina;
+    LINA_REQUIRE(xp && pe && txt_len && att && vv && (x || x_packed), "lina_pe_softmax_weighted_rows_add_ragged: null pointer");
+    LINA_REQUIRE(B > 0 && Tn > 0 && Tn <= kCaMaxT, "lina_pe_softmax_weighted_rows_add_ragged: 0 < T_txt <= %d", kCaMaxT);
+    LINA_REQUIRE(d > 0 && d % 4 == 0 && d <= 8192, "lina_pe_softmax_weighted_rows_add_ragged: d must be a multiple of 4 (<= 8192)");
+    LINA_REQUIRE(pe_sb >= 0, "lina_pe_softmax_weighted_rows_add_ragged: negative table stride");
+    LINA_REQUIRE(valid_dtype(dtype), "lina_pe_softmax_weighted_rows_add_ragged: bad dtype %d", dtype);
+    LINA_REQUIRE((!xp_packed && !x_packed) || d % (dtype == LINA_BF16 ? 32 : 16) == 0,
+                 "lina_pe_softmax_weighted_rows_add_ragged: packed operands need whole k-steps");
+    dim3 grid((unsigned)(B >= 256 ? 1 : (d + 255) / 256), (unsigned)B);   // as lina_pe_softmax_weighted_rows_add
+    const size_t smem = sizeof(float) * (size_t)d;
+    if (dtype == LINA_F32)
+        LINA_LAUNCH((pe_softmax_weighted_rows_ragged_kernel<float>), grid, dim3(256), smem, stream, (const float*)xp, xp_packed,
+                    (const float*)pe, pe_sb, txt_len, scale, (float*)att, att_sb, (const float*)vv, (float*)x, Tn, d,
+                    (float*)x_packed, att_step, att_step_stride, att_steps);
+    else
+        LINA_LAUNCH((pe_softmax_weighted_rows_ragged_kernel<bf16_t>), grid, dim3(256), smem, stream, (const bf16_t*)xp,
+                    xp_packed, (const bf16_t*)pe, pe_sb, txt_len, scale, (bf16_t*)att, att_sb, (const bf16_t*)vv,
+                    (bf16_t*)x, Tn, d, (bf16_t*)x_packed, att_step, att_step_stride, att_steps);
+    return check_launch("lina_pe_softmax_weighted_rows_add_ragged");
 }
 
 #ifdef LINA_SKINNY_PROF

@@ -171,12 +171,26 @@ class _BlockPack:
             self.hv = torch.zeros(self.window, B * self.H, self.Dv, dtype=torch.float32, device=dev)
 
 
-class _Part:
-    """Rows [lo, hi) of the batch: own residual/workspace buffers and state slices, shared weights."""
+def text_lengths(x_lens, B: int, Tn: int) -> list:
+    """``x_lens`` (LongTensor or sequence of B ints) -> list of ints, each in [1, Tn]; ValueError otherwise."""
+    if isinstance(x_lens, torch.Tensor) and x_lens.dim() != 1:
+        raise ValueError("x_lens must be 1-D: one text length per row")
+    lens = x_lens.tolist() if isinstance(x_lens, torch.Tensor) else list(x_lens)
+    if len(lens) != B:
+        raise ValueError(f"x_lens has {len(lens)} entries for {B} rows")
+    if any(int(L) != L or not 1 <= int(L) <= Tn for L in lens):
+        raise ValueError(f"every text length must be an integer in [1, {Tn}] (the padded text width)")
+    return [int(L) for L in lens]
 
-    def __init__(self, lo, hi, packs, kk, vv, d, dtype, dev):
+
+class _Part:
+    """Rows [lo, hi) of the batch: own residual/workspace buffers and state slices, shared weights.  Ragged text: ``pe`` the
+    rows' positional tables [rows, Tn, d] (or one shared [Tn, d] table) and ``txt_len`` their text lengths (int32 [rows])."""
+
+    def __init__(self, lo, hi, packs, kk, vv, d, dtype, dev, pe=None, txt_len=None):
         self.lo, self.hi, self.packs = lo, hi, packs
         self.kk, self.vv = kk, vv
+        self.pe, self.txt_len = pe, txt_len
         self.x = torch.zeros(hi - lo, d, dtype=dtype, device=dev)       # residual stream
         self.xp = torch.zeros(hi - lo, d, dtype=dtype, device=dev)      # pos_net stream
         self.x_p = torch.zeros(ops.packed_numel(hi - lo, d), dtype=dtype, device=dev)    # fragment-major copies
@@ -203,8 +217,13 @@ class DecodeEngine:
                  use_graph: Optional[bool] = None, n_split: Optional[int] = None, fuse_norm: bool = True,
                  window: Optional[int] = None, stream_weights=("in", "up"), cross: str = "spread",
                  fused_pick: bool = True, packed: bool = True, cross_tail_fused: bool = True,
-                 share_weights_with: Optional["DecodeEngine"] = None, state_dtype: Optional[torch.dtype] = None):
-        """``share_weights_with``: another engine of the same model whose packed decode-time weights this one reuses
+                 share_weights_with: Optional["DecodeEngine"] = None, state_dtype: Optional[torch.dtype] = None,
+                 x_lens=None):
+        """``x_lens`` (B ints, 1 <= L_b <= Ttxt): the rows' texts are right-padded to x_enc's width and row b's ends at L_b --
+        the cross-attention of row b then runs over its own L_b positions with a positional table of its own (the ragged
+        launches of the default step; ``cross="fused"`` and ``cross_tail_fused=False`` take no lengths).  ``x_enc`` must come
+        from the text encoder run with the matching mask (LinaModel.generate_batch(x_lens=...) does that).
+        ``share_weights_with``: another engine of the same model whose packed decode-time weights this one reuses
         (DecodeEngineGroup: several engines on row ranges of one batch).
         Every variant of the step is a constructor argument (rounds 2-3 read ``LINA_DECODE_*`` environment switches here).
         ``stream_weights``: which weight matrices of the device loop ("in", "o", "up", "down", "head") are loaded with the
@@ -268,21 +287,37 @@ class DecodeEngine:
         self._cross_spread = cross == "spread"
         self._fused_pick, self._packed_ok = bool(fused_pick), bool(packed)
         self._cross_tail_fused = bool(cross_tail_fused)   # x_pos . pe^T folded into the softmax + att2 . V launch (d % 256 == 0)
+        self._ragged = x_lens is not None
+        if self._ragged and not (self._cross_spread and self._cross_tail_fused):
+            raise ValueError("x_lens (ragged text) runs on the default cross-attention step: cross='spread', cross_tail_fused=True")
         blocks = list(rnn.encoder) + list(rnn.decoder) + [rnn.cross_att.pos_net]
         self.n_enc = len(rnn.encoder)
         ca = rnn.cross_att
         self.ca = ca
-        kk, vv, pe = ca.prepare(x_enc)                                   # [B,1,Ttxt,d] x2, [1,1,Ttxt,d]
+        self._txt_len = self._pe_rows = None
+        if self._ragged:
+            lens = text_lengths(x_lens, batch_size, x_enc.shape[1])
+            self._txt_len = torch.tensor(lens, dtype=torch.int32, device=self.dev)   # static: reset(x_lens=) rewrites it
+            kk, vv, pe = ca.prepare(x_enc, lens=torch.tensor(lens))       # [B,1,Ttxt,d] x2, [B|1,1,Ttxt,d] (zero past L_b)
+        else:
+            kk, vv, pe = ca.prepare(x_enc)                               # [B,1,Ttxt,d] x2, [1,1,Ttxt,d]
         kk, vv = kk.squeeze(1).contiguous(), vv.squeeze(1).contiguous()
         if kk.shape[0] != batch_size:                                    # one text for every row
             kk, vv = kk.expand(batch_size, -1, -1).contiguous(), vv.expand(batch_size, -1, -1).contiguous()
         self._kk, self._vv = kk, vv                                      # static: reset(x_enc) rewrites them in place
-        self.pe = pe.squeeze(1).squeeze(0).contiguous()                  # [Ttxt, d]
-        self.Tn = self.pe.shape[0]
-        Tp = (self.Tn + 31) // 32 * 32
-        self.pe_pad = torch.zeros(Tp, self.pe.shape[1], dtype=self.pe.dtype, device=self.pe.device)
-        self.pe_pad[:self.Tn] = self.pe                                   # weight rows of  scores2 = xp . pe^T
-        self.peT = self.pe_pad.t().contiguous()                           # [d, Tp]: weight rows of  xp = att1 . pe
+        if self._ragged:
+            # a table per row ([B, Ttxt, d], ConvPos: each at its own width -- at B = 1 too) or one shared [Ttxt, d] table (SinPos)
+            pe = pe.squeeze(1)
+            self._pe_rows = pe.contiguous() if ca.per_row_table else pe[0].contiguous()
+            self.pe = self.pe_pad = self.peT = self.pe_pad_p = None      # (the uniform forms' operands)
+            self.Tn = kk.shape[1]
+        else:
+            self.pe = pe.squeeze(1).squeeze(0).contiguous()              # [Ttxt, d]
+            self.Tn = self.pe.shape[0]
+            Tp = (self.Tn + 31) // 32 * 32
+            self.pe_pad = torch.zeros(Tp, self.pe.shape[1], dtype=self.pe.dtype, device=self.pe.device)
+            self.pe_pad[:self.Tn] = self.pe                               # weight rows of  scores2 = xp . pe^T
+            self.peT = self.pe_pad.t().contiguous()                       # [d, Tp]: weight rows of  xp = att1 . pe
         self.att_scale = 1.0 / math.sqrt(kk.shape[-1])
         self.ca_qw, self.ca_qb = ca.q.weight.contiguous(), ca.q.bias.float().contiguous()
         hw = model.logits_head.weight
@@ -290,7 +325,8 @@ class DecodeEngine:
         self.w_head = hw.reshape(self.Q * self.L, self.d).contiguous()
         self.w_head_p = ops.pack_rows(self.w_head)
         self.ca_qw_p = ops.pack_rows(self.ca_qw)
-        self.pe_pad_p = ops.pack_rows(self.pe_pad)
+        if not self._ragged:
+            self.pe_pad_p = ops.pack_rows(self.pe_pad)
         self.use_graph = (self.dev.type == "cuda") if use_graph is None else use_graph
         if n_split is None:
             # measured on MI355X (B=64): 1 range 1.035 ms/step, 2 ranges 1.013 ms, 4 ranges 1.64 ms -- the forked
@@ -305,7 +341,11 @@ class DecodeEngine:
             packs = [_BlockPack(b, self._state[j], lo, hi, shared=None if first is None else first[j],
                                 window=self.window) for j, b in enumerate(blocks)]
             first = first or packs
-            self.parts.append(_Part(lo, hi, packs, kk[lo:hi], vv[lo:hi], self.d, hw.dtype, self.dev))
+            ragged = {}
+            if self._ragged:
+                ragged = dict(pe=self._pe_rows[lo:hi] if ca.per_row_table else self._pe_rows,
+                              txt_len=self._txt_len[lo:hi])
+            self.parts.append(_Part(lo, hi, packs, kk[lo:hi], vv[lo:hi], self.d, hw.dtype, self.dev, **ragged))
         self.packs = self.parts[0].packs
         self._streams = ([torch.cuda.Stream(device=self.dev) for _ in self.parts]
                          if (len(self.parts) > 1 and self.dev.type == "cuda") else None)
@@ -387,6 +427,18 @@ class DecodeEngine:
             q_lin = ops.linear_skinny_packed(part.x_p, self.ca_qw_p, B, self.d, self.d, c2=self.ca_qb, out=part.q_lin)
         else:
             q_lin = ops.linear_skinny(x, self.ca_qw, c2=self.ca_qb, out=part.q_lin)
+        if self._ragged:
+            # right-padded texts: the same three launches in their ragged forms -- row b's scores, softmaxes and weighted sums
+            # over its own L_b positions with its own positional table, att rows zero past L_b (any d % 4 == 0)
+            ops.cross_scores_ragged(q_lin, ca.ln_q.weight, ca.ln_q.bias, ca.ln_q.eps, part.kk, part.scores, self.att_scale,
+                                    part.txt_len)
+            ops.softmax_pe_rows_ragged(part.scores, att[:, 0, 0], part.pe, part.xp, part.txt_len,
+                                       xp_packed=part.xp_p if packed else None, **log_kw)
+            self._block(part.xp, part.packs[-1], lazy, part.xp_p if packed else None)
+            ops.pe_softmax_weighted_rows_add_ragged(part.xp_p if packed else part.xp, part.pe, self.att_scale, att[:, 1, 0],
+                                                    part.vv, x, part.txt_len, x_packed=part.x_p if packed else None,
+                                                    xp_is_packed=packed, **log_kw)
+            return
         if self._cross_spread:
             # scores on 256 workgroups (4 per row), then softmax + att1 . pe in one launch (K = T_txt: no MFMA needed)
             ops.cross_scores(q_lin, ca.ln_q.weight, ca.ln_q.bias, ca.ln_q.eps, part.kk, part.scores, self.att_scale)
@@ -638,7 +690,7 @@ class DecodeEngine:
         L.att_log = torch.zeros(self.B, 2, L.cap, self.Tn, dtype=hw_dt, device=self.dev) if log_att else None
         # the two cross-attention launches of the default step write their rows straight into the log at the device step
         # index; the other forms of the step write the engine's static [B,2,1,Ttxt] buffer and one index_copy_ files it
-        L.att_direct = bool(log_att and self._cross_spread and self._cross_tail_fused and self.d % 256 == 0)
+        L.att_direct = bool(log_att and self._cross_spread and self._cross_tail_fused and (self.d % 256 == 0 or self._ragged))
         if log_hidden:
             if len(self.parts) != 1:
                 raise ValueError("log_hidden needs the engine on one row range")
@@ -733,7 +785,7 @@ class DecodeEngine:
         for part in self.parts:
             part.packs = []
         self.parts, self.packs, self._state = [], [], None
-        self._kk = self._vv = self._logits = self._att = self._y_in = None
+        self._kk = self._vv = self._logits = self._att = self._y_in = self._txt_len = self._pe_rows = None
         self.model = None
 
     # names older callers / tests look at
@@ -826,16 +878,25 @@ class DecodeEngine:
         return L.hid_log[:n].view(n, self.B, self.d).clone()
 
     # ------------------------------------------------------------------ engine reuse
-    def reset(self, x_enc: Optional[torch.Tensor] = None, state: Optional[Cache] = None):
+    def reset(self, x_enc: Optional[torch.Tensor] = None, state: Optional[Cache] = None, x_lens=None):
         """Back to the start of an utterance batch: recurrent states and conv caches zeroed (or copied from ``state``, a
         Cache of the reference layout), and -- with ``x_enc`` -- the text side of the cross-attention recomputed into the
-        engine's static buffers.  The captured graphs stay valid: they only know buffer addresses."""
+        engine's static buffers; ``x_lens`` (an engine built with x_lens): the rows' new text lengths and positional tables,
+        written in place (None: the lengths stay).  The captured graphs stay valid: they only know buffer addresses."""
+        if x_lens is not None and not self._ragged:
+            raise ValueError("reset: x_lens needs an engine built with x_lens (ragged text)")
         if x_enc is not None:
             if x_enc.shape[1] != self.Tn:
                 raise ValueError("reset: the text length is part of the captured step (build another engine)")
             kk, vv, _ = self.ca.prepare(x_enc)
             self._kk.copy_(kk.squeeze(1))
             self._vv.copy_(vv.squeeze(1))
+        if x_lens is not None:
+            lens = text_lengths(x_lens, self.B, self.Tn)
+            self._txt_len.copy_(torch.tensor(lens, dtype=torch.int32))
+            if self.ca.per_row_table:                     # (a shared table does not depend on the lengths)
+                pos = torch.arange(self.Tn, device=self.dev).unsqueeze(0)
+                self._pe_rows.copy_(self.ca.pos_table_rows(pos, torch.tensor(lens)))
         self._lazy_live = False                       # pending window steps of the previous utterances are dropped
         for li, st in enumerate(self._state.states):
             for j, dst in enumerate(st):
@@ -945,16 +1006,17 @@ class DecodeEngineGroup:
     loop ends when EVERY engine's control block says all of its rows have stopped, and the logs are trimmed at the last of those
     steps -- the step the reference's single loop breaks at.  No codec-prompt preload (the caller uses one engine for that)."""
 
-    def __init__(self, model, x_enc: torch.Tensor, batch_size: int, n_engines: int = 2, **engine_args):
+    def __init__(self, model, x_enc: torch.Tensor, batch_size: int, n_engines: int = 2, x_lens=None, **engine_args):
         from .shard import shard_rows
         if n_engines < 2 or n_engines > batch_size:
             raise ValueError("DecodeEngineGroup needs 2 <= n_engines <= batch_size")
         self.B, self.dev = batch_size, x_enc.device
         self.ranges = [shard_rows(batch_size, i, n_engines) for i in range(n_engines)]
+        lens = None if x_lens is None else text_lengths(x_lens, batch_size, x_enc.shape[1])   # (each engine: its slice)
         self.engines = []
         for lo, hi in self.ranges:
             xe = x_enc[lo:hi] if x_enc.shape[0] == batch_size else x_enc
-            self.engines.append(DecodeEngine(model, xe, batch_size=hi - lo,
+            self.engines.append(DecodeEngine(model, xe, batch_size=hi - lo, x_lens=None if lens is None else lens[lo:hi],
                                              share_weights_with=self.engines[0] if self.engines else None, **engine_args))
         self.Q, self.Tn = self.engines[0].Q, self.engines[0].Tn
         self.streams = ([torch.cuda.Stream(device=self.dev) for _ in self.engines] if self.dev.type == "cuda" else None)
@@ -983,8 +1045,10 @@ class DecodeEngineGroup:
             for st in self.streams:
                 main.wait_stream(st)
 
-    def reset(self, x_enc: Optional[torch.Tensor] = None):
-        self._each(lambda e, lo, hi: e.reset(None if x_enc is None else (x_enc[lo:hi] if x_enc.shape[0] == self.B else x_enc)))
+    def reset(self, x_enc: Optional[torch.Tensor] = None, x_lens=None):
+        lens = None if x_lens is None else text_lengths(x_lens, self.B, self.Tn)
+        self._each(lambda e, lo, hi: e.reset(None if x_enc is None else (x_enc[lo:hi] if x_enc.shape[0] == self.B else x_enc),
+                                             x_lens=None if lens is None else lens[lo:hi]))
         self._join()
 
     def begin_greedy(self, max_steps: int, y0: Optional[torch.Tensor] = None, seed: int = 0, **kw):

@@ -727,6 +727,98 @@ def softmax_pe_rows(scores, att, pe, xp, xp_packed=None, att_step=None, att_step
                                        _ptr(xp_packed), B, Tn, d, _dt(pe), be.stream(pe)))
 
 
+# --------------------------------------------------------------------------- ragged text (per-row lengths)
+def _txt_len_arg(txt_len, B: int, Tn: int):
+    """The device lengths of the ragged launches: int32 [B] (values 1 <= L_b <= Tn are the caller's promise -- a device
+    tensor is not read back here; the kernels clamp to that range)."""
+    if txt_len is None or txt_len.dtype != torch.int32 or txt_len.dim() != 1 or txt_len.shape[0] != B \
+            or not txt_len.is_contiguous():
+        raise TypeError("txt_len must be a contiguous int32 [B] tensor of text lengths")
+    if not 0 < Tn <= 1024:
+        raise ValueError("ragged cross-attention: 0 < T_txt <= 1024")
+
+
+def _pe_rows_arg(pe, B: int, Tn: int, d: int):
+    """(table, row stride): a shared [>= Tn, d] table (stride 0) or one [B, >= Tn, d] table per row."""
+    if pe.dim() == 2:
+        if pe.shape[0] < Tn or pe.shape[1] != d or not pe.is_contiguous():
+            raise ValueError("pe must be a contiguous [>= T_txt, d] table or [B, >= T_txt, d] tables")
+        return 0
+    if pe.dim() != 3 or pe.shape[0] != B or pe.shape[1] < Tn or pe.shape[2] != d or pe.stride(2) != 1 \
+            or pe.stride(1) != d:
+        raise ValueError("pe must be a contiguous [>= T_txt, d] table or [B, >= T_txt, d] tables")
+    return pe.stride(0)
+
+
+def cross_scores_ragged(q_lin, ln_w, ln_b, ln_eps, kk, scores, scale, txt_len):
+    """cross_scores for right-padded texts: scores[b,t] for t < txt_len[b] only (kk rows t >= txt_len[b] are not read,
+    scores[b, txt_len[b]:] is not written); see lina_cross_scores_ragged."""
+    be = _backend._BACKEND
+    be.require(q_lin, ln_w, ln_b, kk, scores, txt_len)
+    B, d = q_lin.shape
+    Tn = kk.shape[1]
+    if kk.shape != (B, Tn, d) or not kk.is_contiguous() or kk.dtype != q_lin.dtype:
+        raise ValueError("kk must be a contiguous [B, T_txt, d] tensor of q_lin's dtype")
+    if scores.dtype != torch.float32 or scores.shape != (B, Tn) or not scores.is_contiguous():
+        raise TypeError("scores must be a contiguous fp32 [B, T_txt] tensor")
+    _txt_len_arg(txt_len, B, Tn)
+    _check(be.lib.lina_cross_scores_ragged(_ptr(q_lin), _ptr(ln_w), _ptr(ln_b), float(ln_eps), _ptr(kk), _ptr(scores),
+                                           _ptr(txt_len), B, Tn, d, float(scale), _dt(q_lin), be.stream(q_lin)))
+
+
+def softmax_pe_rows_ragged(scores, att, pe, xp, txt_len, xp_packed=None, att_step=None, att_step_stride: int = 0,
+                           att_steps: int = 0):
+    """softmax_pe_rows for right-padded texts: att[b,:L_b] = softmax(scores[b,:L_b]), att[b,L_b:Tn] = 0,
+    xp[b,:] = att[b,:L_b] . pe_b[:L_b,:] with pe_b = pe ([Tn', d], shared) or pe[b] ([B, Tn', d], one table per row);
+    L_b = txt_len[b].  Tn = scores.shape[1] = the att rows' width."""
+    be = _backend._BACKEND
+    be.require(scores, att, pe, xp, xp_packed, txt_len)
+    B, Tn = scores.shape
+    d = pe.shape[-1]
+    if scores.dtype != torch.float32 or scores.stride(1) != 1:
+        raise TypeError("scores must be fp32 [B, Tn] with contiguous rows")
+    if att.dtype != pe.dtype or xp.dtype != pe.dtype or xp.shape != (B, d) or not xp.is_contiguous():
+        raise TypeError("att / pe / xp must share the model dtype; xp [B, d] contiguous")
+    if att.shape[0] != B or att.shape[-1] < Tn or att.stride(-1) != 1:
+        raise ValueError("att must hold [B, >= Tn] rows")
+    pe_sb = _pe_rows_arg(pe, B, Tn, d)
+    _txt_len_arg(txt_len, B, Tn)
+    if xp_packed is not None and xp_packed.numel() < packed_numel(B, d):
+        raise ValueError("packed xp buffer is too small")
+    be.require(att_step)
+    _check(be.lib.lina_softmax_pe_rows_ragged(_ptr(scores), scores.stride(0), _ptr(att), att.stride(0),
+                                              *_att_log_args(att, att_step, att_step_stride, att_steps), _ptr(pe), pe_sb,
+                                              _ptr(txt_len), _ptr(xp), _ptr(xp_packed), B, Tn, d, _dt(pe), be.stream(pe)))
+
+
+def pe_softmax_weighted_rows_add_ragged(xp, pe, scale, att, vv, x, txt_len, x_packed=None, xp_is_packed: bool = False,
+                                        att_step=None, att_step_stride: int = 0, att_steps: int = 0):
+    """pe_softmax_weighted_rows_add for right-padded texts: scores, softmax and att . vv over t < L_b = txt_len[b],
+    att[b,L_b:Tn] = 0; ``pe`` one shared [Tn', d] table or [B, Tn', d] tables (one per row); any d % 4 == 0."""
+    be = _backend._BACKEND
+    be.require(xp, pe, att, vv, x, x_packed, txt_len)
+    B, Tn, d = vv.shape
+    if pe.dtype != vv.dtype or att.dtype != vv.dtype or xp.dtype != vv.dtype:
+        raise TypeError("xp / pe / att / vv must share the model dtype")
+    if not vv.is_contiguous():
+        raise ValueError("vv must be a contiguous [B, T_txt, d] tensor")
+    if att.shape[0] != B or att.shape[-1] < Tn or att.stride(-1) != 1:
+        raise ValueError("att must hold [B, >= T_txt] rows")
+    pe_sb = _pe_rows_arg(pe, B, Tn, d)
+    _txt_len_arg(txt_len, B, Tn)
+    if xp_is_packed and xp.numel() < packed_numel(B, d):
+        raise ValueError("packed xp buffer is too small")
+    if not xp_is_packed and (xp.shape != (B, d) or not xp.is_contiguous()):
+        raise ValueError("xp must be a contiguous [B, d] tensor")
+    if x_packed is not None and x_packed.numel() < packed_numel(B, d):
+        raise ValueError("packed x buffer is too small")
+    be.require(att_step)
+    _check(be.lib.lina_pe_softmax_weighted_rows_add_ragged(
+        _ptr(xp), 1 if xp_is_packed else 0, _ptr(pe), pe_sb, _ptr(txt_len), float(scale), _ptr(att), att.stride(0),
+        *_att_log_args(att, att_step, att_step_stride, att_steps), _ptr(vv), _ptr(x), _ptr(x_packed), B, Tn, d, _dt(vv),
+        be.stream(vv)))
+
+
 def softmax_rows(x, scale, att, attc, Tn):
     """att[b,:Tn] = softmax(x[b,:Tn]*scale) into the strided `att` rows and the contiguous padded copy attc [B,Tp]."""
     be = _backend._BACKEND

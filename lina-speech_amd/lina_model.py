@@ -120,29 +120,32 @@ class LinaModel(nn.Module):
         stats = torch._foreach_norm(ps) + torch._foreach_norm(torch._foreach_clamp_min(ps, 0))
         return tuple(torch.stack(stats).float().cpu().tolist())
 
-    def _decode_engine(self, x_enc: Tensor, B: int, init_state, n_engines: int = 1, state_dtype=None):
+    def _decode_engine(self, x_enc: Tensor, B: int, init_state, n_engines: int = 1, state_dtype=None, x_lens=None):
         """The DecodeEngine of (batch size, text length, dtype, device, current weights), built once and re-armed for
         every later ``generate_batch`` call of the same shape: construction packs 0.3 GB of weights and captures two
         hipGraphs (~0.6 k kernel nodes), far more than a call at B = 64 should pay.  "Current weights" = every
-        parameter's (storage, version) AND a content fingerprint (see ``_weights_fingerprint``)."""
+        parameter's (storage, version) AND a content fingerprint (see ``_weights_fingerprint``).  ``x_lens`` (ragged
+        text): an engine of the ragged step -- part of the key as a flag; the lengths themselves are re-armed in place."""
         from .decode import DecodeEngine, DecodeEngineGroup
         w = self.logits_head.weight
         key = (B, int(n_engines), int(x_enc.shape[1]), w.dtype, str(w.device), str(state_dtype),
                tuple((p.data_ptr(), -1 if p.is_inference() else p._version) for p in self.parameters()),
-               self._weights_fingerprint())
+               self._weights_fingerprint()) + (("ragged",) if x_lens is not None else ())
         cache = self.__dict__.setdefault("_decode_engines", {})
         eng = cache.pop(key, None)
         if eng is None:
             if n_engines > 1:                                        # (no init_state / prompt in this form: the caller checked)
-                eng = DecodeEngineGroup(self, x_enc, batch_size=B, n_engines=n_engines, state_dtype=state_dtype)
+                eng = DecodeEngineGroup(self, x_enc, batch_size=B, n_engines=n_engines, state_dtype=state_dtype,
+                                        x_lens=x_lens)
             else:
-                eng = DecodeEngine(self, x_enc, batch_size=B, state_dtype=state_dtype)   # NotImplementedError: architecture not covered
+                eng = DecodeEngine(self, x_enc, batch_size=B, state_dtype=state_dtype,   # NotImplementedError: architecture
+                                   x_lens=x_lens)                                         # not covered
                 if init_state is not None:
                     eng.reset(state=init_state)
         elif n_engines > 1:
-            eng.reset(x_enc)
+            eng.reset(x_enc, x_lens=x_lens)
         else:
-            eng.reset(x_enc, state=init_state)
+            eng.reset(x_enc, state=init_state, x_lens=x_lens)
         cache[key] = eng                                             # most recently used last
         while len(cache) > self._ENGINE_CACHE_SIZE:
             cache.pop(next(iter(cache))).close()                     # an engine is a reference cycle: free its device memory now
@@ -153,7 +156,7 @@ class LinaModel(nn.Module):
                        max_seqlen: int = 1000, k: int = 100, first_greedy_quant: int = 1, temp: float = 1.0,
                        init_state=None, force_max_seqlen: bool = False, stop_check_every: int = 16,
                        engine: Optional[str] = None, seed: Optional[int] = None, n_engines: Optional[int] = None,
-                       state_dtype: Optional[torch.dtype] = None):
+                       state_dtype: Optional[torch.dtype] = None, *, x_lens=None):
         """Reference model/modeling_lina.py:111-192 (same arguments, same four returns).  ``engine``:
           None / "auto" -- the device-side loop (decode.DecodeEngine.generate: one hipGraph replay per 8 tokens, picks /
                            stop flags / attention log / next-token embedding inside the graph) when the architecture is
@@ -168,10 +171,22 @@ class LinaModel(nn.Module):
         ``state_dtype`` (device loop, bf16 models; opt-in): ``torch.bfloat16`` keeps the recurrent state in bf16 and rounds it
         after every step, as the reference itself does for a bf16 model (model/gla.py:229-240 + Cache.update); default fp32.
         ``seed`` feeds the device-side sampler of the loop (default: drawn from torch's generator, so
-        ``torch.manual_seed`` makes a call reproducible, like the reference's multinomial)."""
+        ``torch.manual_seed`` makes a call reproducible, like the reference's multinomial).
+        ``x_lens`` (keyword only; ours): texts of different lengths in one batch -- ``x`` [B, Tmax] right-padded and row i's
+        text ends at ``x_lens[i]`` (1 <= x_lens[i] <= Tmax; LongTensor or list).  ``x`` may also be a list of B 1-D texts
+        (padded with 0 here, lengths derived; ``batch_size`` must equal len(x)).  Row i then decodes as
+        ``generate_batch(x[i, :x_lens[i]], batch_size=1)`` would: the text encoder masks the padding, both attentions of the
+        cross-attention run over the row's own positions with a positional table at its own width, the attention log holds
+        zeros at the padding and row i's cut is trimmed to its text.  All lengths == Tmax: the uniform path, unchanged."""
         B, Q = batch_size, self.n_quant
+        x, lens = self._ragged_text(x, B, x_lens)
         x = (x.unsqueeze(0).expand(B, -1) if x.dim() == 1 else x).to(device)   # 1-D: one text for every row
-        x_enc = self.txt_encoder(self.txt_embed(x))
+        enc_mask = cross_mask = None
+        if lens is not None:                                    # the reference's collate masks (initial_state.py:65-70)
+            live = torch.arange(x.shape[1], device=device)[None, :] < lens.to(device)[:, None]             # [B, Tmax]
+            enc_mask = live[:, None, :] & live[:, :, None]
+            cross_mask = live[:, None, :]                                                                   # [B, 1, Tmax]
+        x_enc = self.txt_encoder(self.txt_embed(x), mask=enc_mask)
         y_embd = self.rvq_embed.embed_sum(torch.ones(Q, B, 1, dtype=torch.long, device=device))
 
         p_len = -1
@@ -192,7 +207,7 @@ class LinaModel(nn.Module):
                 n_engines = 2 if B >= self.AUTO_TWO_ENGINES_ROWS else 1
             n_eng = n_engines if (n_engines > 1 and prompt is None and init_state is None and B >= 2 * n_engines) else 1
             try:
-                eng = self._decode_engine(x_enc, B, init_state, n_eng, state_dtype)
+                eng = self._decode_engine(x_enc, B, init_state, n_eng, state_dtype, x_lens=lens)
             except NotImplementedError:
                 if mode == "loop":
                     raise
@@ -202,21 +217,23 @@ class LinaModel(nn.Module):
                 seed = int(torch.randint(0, 2 ** 62, (1,)))
             qs, atts, n = eng.generate(max_seqlen, y_embd, k=k, temp=temp, first_greedy_quant=first_greedy_quant, seed=seed,
                                        force_max_seqlen=force_max_seqlen, stop_check_every=stop_check_every, log_att=True)
-            return self._finish_generate(qs, atts, (qs == 2).all(dim=0), B, device)
+            return self._finish_generate(qs, atts, (qs == 2).all(dim=0), B, device, lens)
+        # (ragged text: the module path and the prompt prefill need the per-row positional tables of prepare(lens=))
+        ragged_prepared = None if lens is None else self.attentive_rnn.cross_att.prepare(x_enc, lens=lens)
         if eng is not None:
-            state, prepared, step_fn = eng.state, None, None
+            state, prepared, step_fn = eng.state, ragged_prepared, None
         elif mode == "fused":
             from .decode import DecodeEngine
-            step_fn = DecodeEngine(self, x_enc, batch_size=B, state=init_state)
+            step_fn = DecodeEngine(self, x_enc, batch_size=B, state=init_state, x_lens=lens)
             state = step_fn.state
-            prepared = None
+            prepared = ragged_prepared
         else:
             state = init_state if init_state is not None else self.attentive_rnn.init_state(
                 max_seqlen=max_seqlen, batch_size=B)
-            prepared = self.attentive_rnn.cross_att.prepare(x_enc)
+            prepared = ragged_prepared if lens is not None else self.attentive_rnn.cross_att.prepare(x_enc)
 
             def step_fn(y, t):
-                h, att, _ = self.attentive_rnn.step(y, x_enc, t, state, prepared=prepared)
+                h, att, _ = self.attentive_rnn.step(y, x_enc, t, state, prepared=prepared, crossatt_mask=cross_mask)
                 return self.logits_head(h), att
 
         # ---- prompt prefill: the reference feeds the start token and the p_len prompt tokens one step at a time
@@ -228,7 +245,8 @@ class LinaModel(nn.Module):
         if prompt is not None and p_len > 0 and hasattr(self.attentive_rnn, "step"):
             n_pre = min(p_len + 1, max_seqlen)
             y_seq = torch.cat([y_embd, prompt[:, :n_pre - 1]], dim=1)
-            h, pre_att, _ = self.attentive_rnn.step(y_seq, x_enc, 0, state, prepared=prepared)
+            h, pre_att, _ = self.attentive_rnn.step(y_seq, x_enc, 0, state, prepared=prepared,
+                                                    crossatt_mask=None if cross_mask is None else cross_mask.expand(-1, n_pre, -1))
             pre_logits = self.logits_head(h)                        # [B,n_pre,Q,L]
 
         def pick_tokens(logits):                                    # [B,1,Q,L] -> [Q,B,1]
@@ -249,7 +267,7 @@ class LinaModel(nn.Module):
             qs, atts, n = eng.generate(max_seqlen, y0, k=k, temp=temp, first_greedy_quant=first_greedy_quant, seed=seed,
                                        force_max_seqlen=force_max_seqlen, stop_check_every=stop_check_every,
                                        log_att=True, preload=preload)
-            return self._finish_generate(qs, atts, (qs == 2).all(dim=0), B, device)
+            return self._finish_generate(qs, atts, (qs == 2).all(dim=0), B, device, lens)
 
         all_stop = torch.zeros(B, 1, dtype=torch.bool, device=device)
         qs, atts, stop_tokens = [], [], []
@@ -276,14 +294,39 @@ class LinaModel(nn.Module):
             qs, atts, stop_tokens = qs[:stop_at + 1], atts[:stop_at + 1], stop_tokens[:stop_at + 1]
         atts = torch.cat(atts, dim=2) if atts[0] is not None else None
         qs = torch.stack(qs, dim=2).squeeze(-1)                                  # [Q,B,n]
-        return self._finish_generate(qs, atts, torch.cat(stop_tokens, dim=1), B, device)
+        return self._finish_generate(qs, atts, torch.cat(stop_tokens, dim=1), B, device, lens)
 
-    def _finish_generate(self, qs, atts, is_stop, B, device):
+    @staticmethod
+    def _ragged_text(x, B: int, x_lens):
+        """generate_batch's text argument -> (x, lengths [B] LongTensor or None).  A list of B 1-D texts is right-padded with
+        0 and its lengths derived; lengths that are all the padded width mean a uniform batch (None: today's path)."""
+        from .decode import text_lengths
+        if isinstance(x, (list, tuple)):
+            if x_lens is not None:
+                raise ValueError("x_lens: the list form of x carries its own lengths")
+            if len(x) != B:
+                raise ValueError(f"x is a list of {len(x)} texts: batch_size must equal it (got {B})")
+            if any(t.dim() != 1 for t in x):
+                raise ValueError("x as a list: one 1-D LongTensor per row")
+            x_lens = [int(t.shape[0]) for t in x]
+            if min(x_lens) < 1:
+                raise ValueError("every text length must be >= 1")
+            x = torch.nn.utils.rnn.pad_sequence([t.to(x[0].device) for t in x], batch_first=True, padding_value=0)
+        if x_lens is None:
+            return x, None
+        if x.dim() != 2:
+            raise ValueError("x_lens needs x as [B, Tmax] right-padded texts (a 1-D x is one text for every row)")
+        if x.shape[0] != B:
+            raise ValueError(f"x has {x.shape[0]} rows for batch_size {B}")
+        lens = torch.tensor(text_lengths(x_lens, B, x.shape[1]), dtype=torch.long)
+        return x, (None if bool((lens == x.shape[1]).all()) else lens)
+
+    def _finish_generate(self, qs, atts, is_stop, B, device, lens=None):
         """Post-processing of the reference (modeling_lina.py:180-192) from the [B,n] stop flags: the stop-flag matrix
         with the closing column of ones, the un-delayed codes and the per-row cuts.  The reference takes
         ``torch.unique(stop_idx[i])[1]`` row by row (a sort and a host read per row); the set it sorts is {0} plus the
         positions of the row's stop flags, so element [1] is the first position >= 1 that carries a flag -- computed here
-        for all rows at once and read back once."""
+        for all rows at once and read back once.  ``lens`` (ragged text): row i's attention cut ends at its own text."""
         stop_tokens = torch.cat([is_stop.float(), torch.ones(B, 1, device=device)], dim=1)    # [B,n+1]
         n = stop_tokens.shape[1]
         rvq = (undelay_rvq(qs) - self.n_special_token_in).clamp_min(0)
@@ -292,6 +335,7 @@ class LinaModel(nn.Module):
         if n < 2:
             raise IndexError("generate_batch: no step was decoded (max_seqlen == 0)")   # the reference's unique()[1] raises too
         first = torch.where(flagged, pos, torch.full_like(pos, n)).min(dim=1).values.tolist()
-        cuts = [(rvq[:, i:i + 1, :idx - self.n_quant], None if atts is None else atts[i, :, :idx])
+        txt = [None] * B if lens is None else lens.tolist()
+        cuts = [(rvq[:, i:i + 1, :idx - self.n_quant], None if atts is None else atts[i, :, :idx, :txt[i]])
                 for i, idx in enumerate(first)]
         return qs, atts, stop_tokens, cuts

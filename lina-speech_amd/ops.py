@@ -28,6 +28,7 @@ from .kernels import (
     linear_skinny_packed, linear_skinny, gla_decode_inproj, gla_decode_inproj_packed, gla_decode_update_norm,
     gla_decode_window, gla_decode_window_flush, cross_att_step1, cross_att_step2, cross_scores,
     cross_scores_softmax, softmax_weighted_rows_add, pe_softmax_weighted_rows_add, softmax_pe_rows, softmax_rows, weighted_rows_add, dwconv7_ln,
+    cross_scores_ragged, softmax_pe_rows_ragged, pe_softmax_weighted_rows_add_ragged,
     istft_ola)
 from .autograd import (
     _GLAFunction, _needs_grad, _gla, fused_recurrent_gla, naive_recurrent_gla, chunk_gla, fused_chunk_gla,
