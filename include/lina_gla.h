@@ -463,6 +463,22 @@ int lina_gla_decode_window_s(const void* q, const void* k, const void* v, const 
                              int dtype, int g_dtype, float scale, lina_stream_t stream);
 int lina_gla_decode_window_flush_s(void* state, int state_dtype, const float* hist_k, const float* hist_c,
                                    const float* hist_v, int n_pending, int B, int H, int Dk, int Dv, lina_stream_t stream);
+/* lina_gla_decode_window_s as a PERSISTENT launch: n_wg >= 1 workgroups (clamped to B * H), workgroup i serves the heads
+ * i, i + n_wg, ... with the next head's state loads in flight while the current head is updated, stored and reduced.  Same
+ * arguments, same arithmetic in the same order: og, hist_* and state are bit-identical to lina_gla_decode_window_s at every
+ * window position.  A grid smaller than the chip leaves compute units to the launches of other streams.  Served: Dv <= 256,
+ * window <= 8, and at Dk = 256 bf16 activations only (dtype == LINA_BF16) -- anything else returns LINA_ERR_UNSUPPORTED and
+ * launches nothing (o_exchange / counters are not used); n_wg < 1 is LINA_ERR_ARG. */
+int lina_gla_decode_window_persist(const void* q, const void* k, const void* v, const void* gk,
+                                   void* state, int state_dtype, const void* gate, const void* norm_weight,
+                                   void* og, float* o_exchange, int* counters,
+                                   float* hist_k, float* hist_c, float* hist_v,
+                                   const int64_t* step, const int64_t* origin, int window,
+                                   int B, int H, int Dk, int Dv,
+                                   int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh,
+                                   int64_t v_sb, int64_t v_sh, int64_t g_sb, int64_t g_sh,
+                                   int64_t gate_sb, int64_t gate_sh, float eps, int og_packed,
+                                   int dtype, int g_dtype, float scale, int n_wg, lina_stream_t stream);
 
 /* Decode-step projection with fused neighbours: out[M,N] = epi(A[M,K] . W[N,K]^T), M ~ batch rows.
  *   ln_dim > 0 : A is layer-normalised over its ln_dim features first, folded algebraically:

@@ -332,6 +332,295 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_kernel(
     }
 }
 
+// ---- the PERSISTENT form of the kernel above (CS = 1, no flush): a fixed grid of n_wg workgroups, workgroup i serves heads
+// i, i + n_wg, ...  The per-head arithmetic is the kernel's above, operation for operation and in the same order per
+// element (scale, the window's rank updates s = 0 .. j, store, acc over the pieces i = 0 .. NP-1, the s_red sum, the pending
+// window terms, K5), so og, hist_* and S come out bit-identical.  What differs is WHEN memory moves: the NP pieces of a
+// thread's tile go through a register RING of NP / 2 slots -- as soon as a group of PG pieces has been consumed (and, at the
+// write-back position, stored) its registers are reloaded with the pieces half a head further on, of this head or of head
+// n + n_wg, so half a head of loads (128 KiB at L169) stays in flight on the CU across the head boundary and the
+// write-back's stores interleave with the next head's loads instead of following a chip-wide read phase.  The next head's
+// small loads (history, q / k / v / g, gate) are issued BEFORE its tile (a wave's loads return in order) and kept RAW until
+// the bookkeeping that follows the current head's pieces; the LDS arrays are double-buffered (head parity), one barrier
+// pair per head as above: wave 0's K5 tail of head n runs beside the other waves' bookkeeping of head n + 1.  No workgroup
+// waits for another one.
+//
+// The compiler counts the waits (vmcnt) itself, and where paths with different numbers of loads meet it assumes the
+// smallest: a load under an `if` makes every later wait drain the ring.  Hence (a) every lane of every wave issues the SAME
+// small loads -- a row wave c_s and k_s of its rows, the other waves v_s twice, slots past the window position clamped to
+// the last valid one, q / k / g / v / gate at a clamped index whether the lane needs them or not (same cache lines: no HBM
+// bytes); (b) the ring's reloads are unconditional too: on a workgroup's last head they re-read that head's first pieces
+// (cache hits) into registers nobody reads.  Only the write-back's stores sit under a (workgroup-uniform) branch: there a
+// wait can ask for up to PG more of the OLDEST operations than it needs, i.e. for the previous group's first store.  (The
+// body compiled four times, <write-back or not> x <a next head or not>, needs no such branch -- and spilled 80 registers.)
+// Registers: 16 waves at 128 VGPRs fill the CU's register file.  A ring of a whole head (64 VGPRs) plus the next head's
+// history spilled (and a spilled history value is a load waited for where it was issued); half a head in flight is still
+// several times what the CU's share of the HBM rate needs (~25 GB/s x ~2 us).  Everything else has to be small too -- windows
+// up to kWinPersist steps (7 history entries per lane), and every address is a workgroup-uniform base (scalar registers)
+// plus a 32-bit per-lane offset that does not depend on the head.
+constexpr int kWinPersist = 8;
+// uniform base + per-lane BYTE offset (32 bits): the form the compiler turns into a scalar-base memory instruction
+// -- and the offset made OPAQUE at every use: left to itself the compiler adds the lane offset to a loop-invariant part of
+// the base once, keeps one 64-bit address per piece and history slot in vector registers, and spills the ring for them.
+template <typename T> __device__ __forceinline__ T* at_byte(T* base, int byte_off) {
+    opaque(byte_off);
+    return (T*)((const char*)base + (unsigned)byte_off);
+}
+
+template <int DV, int NRB, int CS, typename TIO, typename TG, typename TS = float>
+__global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
+    const TIO* __restrict__ q, const TIO* __restrict__ k, const TIO* __restrict__ v, const TG* __restrict__ gk, TS* S,
+    float* hist_k, float* hist_c, float* hist_v, const int64_t* step, const int64_t* origin, int window, int n_heads,
+    int H, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh, int64_t g_sb,
+    int64_t g_sh, float scale, const TIO* __restrict__ gate, int64_t gate_sb, int64_t gate_sh,
+    const TIO* __restrict__ nw, float eps, TIO* __restrict__ og, int og_packed) {
+    static_assert(CS == 1, "the persistent form serves heads of one column block");
+    constexpr int RB = 64;
+    constexpr int DK = RB * NRB;
+    constexpr int EPL = state_piece<TS>::n;
+    constexpr int CG = DV / EPL;
+    constexpr int RPI = 256 / CG;
+    constexpr int NP = RB / RPI;
+    constexpr int RD = NP >= 2 ? NP / 2 : 1;   // ring depth in pieces: half a head (see "Registers" above)
+    constexpr int PG = RD < 4 ? RD : 4;     // pieces per ring group: one read of the window's v rows serves PG pieces
+    static_assert(NP % RD == 0 && RD % PG == 0, "a head is a whole number of passes over the ring");
+    constexpr int CG4 = DV / 4;
+    constexpr int NH = kWinPersist - 1;     // history entries a launch can read: steps 0 .. window-2 of the window
+    // the arrays of the kernel above, twice (head parity), as ONE object: one base per buffer, constant offsets inside it
+    struct __attribute__((aligned(16))) head_lds {
+        __attribute__((aligned(16))) float v[kWinPersist][DV];
+        __attribute__((aligned(16))) float red[NRB * RPI * DV];
+        float w[kWinPersist][DK];
+        float q[DK], e[DK], a[kWinPersist][NRB];
+        typename raw4<TIO>::type gate[CG4];                     // the head's gate row for wave 0's tail, raw
+    };
+    __shared__ head_lds s_buf[2];
+    __shared__ typename raw4<TIO>::type s_nw[CG4];              // the norm weight: the same for every head
+
+    const int tid = threadIdx.x;
+    const int rb = tid >> 8, t256 = tid & 255;
+    const int cg = t256 % CG, rg = t256 / CG;
+    const int r0 = rb * RB;
+    const int64_t BH = n_heads;
+    const int n_wg = (int)gridDim.x;
+    int bh = blockIdx.x;
+    if (bh >= n_heads) return;              // more workgroups than heads (workgroup-uniform)
+
+    const int j = (int)(step[0] - origin[0]) & (window - 1);
+    const bool write_back = j == window - 1;
+    const int n_hist = j;
+    const int s_last = n_hist > 0 ? n_hist - 1 : 0;
+    constexpr int NV = 192 * NRB;
+    const bool row_wave = wave_uniform(t256 < RB ? 1 : 0) != 0;        // the first wave of each thread group, as a scalar
+    const int row = r0 + (t256 & (RB - 1));
+    const int vc = rb * 192 + t256 - RB;                               // v column of a non-row thread (first pass)
+    const int vcc = vc < 0 ? 0 : (vc < DV ? vc : DV - 1);              // ... clamped: every lane loads
+    // per-lane byte offsets, the same for every head
+    const int toff = ((r0 + rg) * DV + EPL * cg) * (int)sizeof(TS);    // first piece inside a head's state
+    const int hoffl = (row_wave ? row : vcc) * 4;                      // history: c_s / k_s of a row, or v_s of a column
+    const int rowio = row * (int)sizeof(TIO), rowg = row * (int)sizeof(TG), vcio = vcc * (int)sizeof(TIO);
+    const int t4io = (tid & (CG4 - 1)) * 4 * (int)sizeof(TIO);
+    // the distance of two pieces as a scalar the compiler cannot see through: as a constant it is folded behind the lane
+    // offset, (base + lane) + i * 4096, which needs a vector address again
+    int pstep_ = RPI * DV;
+    opaque(pstep_);
+    const int pstep = wave_uniform(pstep_);
+    // history bases of this wave's kind
+    const float* hA = row_wave ? hist_c : hist_v;
+    const float* hB = row_wave ? hist_k : hist_v;
+    const int64_t hw = row_wave ? DK : DV;
+
+    // the small loads of ONE head, raw (a conversion would be a use, i.e. a wait, where the load is issued)
+    float h1[NH], h2[NH];
+    decltype(ld_raw(gk)) gj_r;
+    decltype(ld_raw(q)) kj_r, qj_r, vj_r;
+    typename raw4<TIO>::type gate_r;
+    if (tid < CG4) s_nw[tid] = ld4_raw(nw + 4 * tid);                  // read by wave 0 behind the first head's barriers
+    auto small_loads = [&](int hd) __attribute__((always_inline)) {
+        const int b = hd / H, h = hd % H;
+#pragma unroll
+        for (int s = 0; s < NH; ++s) {
+            const int sc = s < n_hist ? s : s_last;
+            const int64_t o = ((int64_t)sc * BH + hd) * hw;
+            h1[s] = ld_hist(at_byte(hA + o, hoffl));
+            h2[s] = ld_hist(at_byte(hB + o, hoffl));
+        }
+        gj_r = ld_raw(at_byte(gk + (b * g_sb + h * g_sh), rowg));
+        kj_r = ld_raw(at_byte(k + (b * k_sb + h * k_sh), rowio));
+        qj_r = ld_raw(at_byte(q + (b * q_sb + h * q_sh), rowio));
+        vj_r = ld_raw(at_byte(v + (b * v_sb + h * v_sh), vcio));
+        gate_r = ld4_raw(at_byte(gate + (b * gate_sb + h * gate_sh), t4io));
+    };
+
+    float St[RD][EPL];                      // the ring: slot i % RD holds piece i
+    small_loads(bh);
+    {
+        const TS* tile = S + (int64_t)bh * DK * DV;
+#pragma unroll
+        for (int i = 0; i < RD; ++i) ld_state(at_byte(tile + i * pstep, toff), St[i]);
+    }
+
+    // one head: WB = the write-back position, NEXT = this workgroup has another head (nx) after this one
+    auto head = [&](const bool WB, const bool NEXT, const int p, const int nx) __attribute__((always_inline)) {
+        const int b = bh / H, h = bh % H;
+        const int64_t hoff = (int64_t)bh * DK;
+        head_lds& L = s_buf[p];
+        // ---- per-row gate bookkeeping and the window's v rows of head bh -> LDS buffer p
+        if (tid < CG4) L.gate[tid] = gate_r;
+        if (row_wave) {
+            const float gj = cvt1(gj_r), kj = cvt1(kj_r), qj = cvt1(qj_r) * scale;
+            float cprev = 0.0f;
+#pragma unroll
+            for (int s = 0; s < NH; ++s) cprev = (s == j - 1) ? h1[s] : cprev;
+            const float cj = cprev + gj;
+            st_hist(at_byte(hist_c + ((int64_t)j * BH * DK + hoff), row * 4), cj);
+            st_hist(at_byte(hist_k + ((int64_t)j * BH * DK + hoff), row * 4), kj);
+            L.q[row] = qj;
+            L.e[row] = __expf(cj);
+#pragma unroll
+            for (int s = 0; s < kWinPersist; ++s) {
+                if (s <= j) {                                            // workgroup-uniform
+                    const float ws = (s == j) ? kj : __expf(cj - h1[s < NH ? s : 0]) * h2[s < NH ? s : 0];
+                    L.w[s][row] = ws;
+                    float a = qj * ws;                                   // <q (.) e^{c_j - c_s}, k_s> over this row block
+                    a += shfl_xor(a, 1); a += shfl_xor(a, 2); a += shfl_xor(a, 4);
+                    a += shfl_xor(a, 8); a += shfl_xor(a, 16); a += shfl_xor(a, 32);
+                    if (t256 == 0) L.a[s][rb] = a;
+                }
+            }
+        } else {
+            if (vc < DV) {
+                const float vj = cvt1(vj_r);
+#pragma unroll
+                for (int s = 0; s < kWinPersist; ++s)
+                    if (s <= j) L.v[s][vc] = (s == j) ? vj : h1[s < NH ? s : 0];
+                st_hist(at_byte(hist_v + ((int64_t)j * BH + bh) * DV, vc * 4), vj);
+            }
+            for (int c = vc + NV; c < DV; c += NV) {            // only when Dv > 192 * Dk/64 (Dk = 64, Dv = 256)
+                for (int s = 0; s <= j; ++s) {
+                    float vs;
+                    if (s == j) {
+                        vs = ld(v + b * v_sb + h * v_sh + c);
+                        hist_v[((int64_t)j * BH + bh) * DV + c] = vs;
+                    } else {
+                        vs = hist_v[((int64_t)s * BH + bh) * DV + c];
+                    }
+                    L.v[s][c] = vs;
+                }
+            }
+        }
+        __syncthreads();
+
+        // the next head's small loads, before the ring's reloads: they return first.  On the last head the loads go on
+        // all the same -- to this head's first pieces, which the caches hold -- so that the waits stay counted
+        small_loads(NEXT ? nx : bh);
+        TS* tile = S + (int64_t)bh * DK * DV;
+        const TS* tile_nx = NEXT ? S + (int64_t)nx * DK * DV : tile;
+        const int pstep_nx = NEXT ? pstep : 0;
+
+        float acc[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int g0 = 0; g0 < NP; g0 += PG) {                   // pieces g0 .. g0 + PG - 1, in the slots from g0 % RD
+            const int sl = g0 % RD;
+            if (WB) {
+                // S <- e^{c_j} S + sum_s w_s (x) v_s  (the window's rank-(j+1) update), o from the UPDATED rows
+#pragma unroll
+                for (int u = 0; u < PG; ++u) {
+                    const float d = L.e[r0 + rg + RPI * (g0 + u)];
+#pragma unroll
+                    for (int e = 0; e < EPL; ++e) St[sl + u][e] *= d;
+                }
+                for (int s = 0; s <= j; ++s) {
+                    float vv[EPL];
+#pragma unroll
+                    for (int e4 = 0; e4 < EPL; e4 += 4) {
+                        const float4 t = *reinterpret_cast<const float4*>(&L.v[s][EPL * cg + e4]);
+                        vv[e4] = t.x; vv[e4 + 1] = t.y; vv[e4 + 2] = t.z; vv[e4 + 3] = t.w;
+                    }
+#pragma unroll
+                    for (int u = 0; u < PG; ++u) {
+                        const float ws = L.w[s][r0 + rg + RPI * (g0 + u)];
+#pragma unroll
+                        for (int e = 0; e < EPL; ++e) St[sl + u][e] = fmaf(ws, vv[e], St[sl + u][e]);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < PG; ++u) st_state(at_byte(tile + (g0 + u) * pstep, toff), St[sl + u]);
+#pragma unroll
+                for (int u = 0; u < PG; ++u) {
+                    const float qq = L.q[r0 + rg + RPI * (g0 + u)];
+#pragma unroll
+                    for (int e = 0; e < EPL; ++e) acc[e] = fmaf(qq, St[sl + u][e], acc[e]);
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < PG; ++u) {
+                    const int rr = r0 + rg + RPI * (g0 + u);
+                    const float qe = L.q[rr] * L.e[rr];
+#pragma unroll
+                    for (int e = 0; e < EPL; ++e) acc[e] = fmaf(qe, St[sl + u][e], acc[e]);
+                }
+            }
+            // the slots are free: the second half of this head, then the first half of the next one.
+            if (g0 + RD < NP) {
+#pragma unroll
+                for (int u = 0; u < PG; ++u) ld_state(at_byte(tile + (g0 + RD + u) * pstep, toff), St[sl + u]);
+            } else {
+#pragma unroll
+                for (int u = 0; u < PG; ++u) ld_state(at_byte(tile_nx + (g0 + RD - NP + u) * pstep_nx, toff), St[sl + u]);
+            }
+        }
+#pragma unroll
+        for (int e4 = 0; e4 < EPL; e4 += 4)
+            *reinterpret_cast<float4*>(&L.red[(rb * RPI + rg) * DV + EPL * cg + e4]) = make_float4(acc[e4], acc[e4 + 1], acc[e4 + 2], acc[e4 + 3]);
+        __syncthreads();
+        if (tid < 64) {
+            // ---- wave 0 finishes head bh (the sum, the pending window terms, K5) while the other waves go on
+            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (tid < CG4) {
+                r = *reinterpret_cast<const float4*>(&L.red[4 * tid]);
+#pragma unroll
+                for (int jj = 1; jj < NRB * RPI; ++jj) {
+                    const float4 t = *reinterpret_cast<const float4*>(&L.red[jj * DV + 4 * tid]);
+                    r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w;
+                }
+                if (!WB)                // pending window terms: sum_s <q (.) e^{c_j - c_s}, k_s> v_s
+                    for (int s = 0; s <= j; ++s) {
+                        float a = L.a[s][0];
+#pragma unroll
+                        for (int g2 = 1; g2 < NRB; ++g2) a += L.a[s][g2];
+                        const float4 vv = *reinterpret_cast<const float4*>(&L.v[s][4 * tid]);
+                        r.x = fmaf(a, vv.x, r.x); r.y = fmaf(a, vv.y, r.y); r.z = fmaf(a, vv.z, r.z); r.w = fmaf(a, vv.w, r.w);
+                    }
+            }
+            float ss = r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w;
+            ss += shfl_xor(ss, 1); ss += shfl_xor(ss, 2); ss += shfl_xor(ss, 4);
+            ss += shfl_xor(ss, 8); ss += shfl_xor(ss, 16); ss += shfl_xor(ss, 32);
+            if (tid < CG4) {
+                const float rs = rsqrtf(ss / (float)DV + eps);
+                float4 x = r;
+                x.x *= rs; x.y *= rs; x.z *= rs; x.w *= rs;
+                const float4 ww = cvt4(s_nw[tid]), gg = cvt4(L.gate[tid]);
+                x.x *= ww.x; x.y *= ww.y; x.z *= ww.z; x.w *= ww.w;
+                x.x *= gg.x * sigmoidf(gg.x); x.y *= gg.y * sigmoidf(gg.y);
+                x.z *= gg.z * sigmoidf(gg.z); x.w *= gg.w * sigmoidf(gg.w);
+                if (og_packed) st4(og + packed_off<TIO>(b, h * DV + 4 * tid, H * DV), x);
+                else st4(og + (int64_t)bh * DV + 4 * tid, x);
+            }
+        }
+    };
+
+    for (int p = 0;; p ^= 1) {
+        const int nx = bh + n_wg;
+        const bool has_next = nx < n_heads;
+        head(write_back, has_next, p, nx);
+        if (!has_next) break;
+        bh = nx;
+    }
+}
+
 template <typename TIO, typename TG, typename TS = float>
 static int launch_window(const void* q, const void* k, const void* v, const void* gk, TS* S, float* hk, float* hc,
                          float* hv, const int64_t* step, const int64_t* origin, int window, int flush_n, int B, int H,
@@ -363,6 +652,40 @@ static int launch_window(const void* q, const void* k, const void* v, const void
 #undef LINA_WIN_CASE
 #undef LINA_WIN_ONE
     return check_launch("lina_gla_decode_window");
+}
+
+template <typename TIO, typename TG, typename TS>
+static int launch_window_persist(const void* q, const void* k, const void* v, const void* gk, TS* S, float* hk, float* hc,
+                                 float* hv, const int64_t* step, const int64_t* origin, int window, int n_wg, int B, int H,
+                                 int Dk, int Dv, const int64_t* st, float scale, lina_stream_t stream, const void* gate,
+                                 int64_t gate_sb, int64_t gate_sh, const void* nw, float eps, void* og, int og_packed) {
+    const int n_heads = B * H;
+    dim3 grid((unsigned)(n_wg < n_heads ? n_wg : n_heads));
+#define LINA_WINP_ONE(DVV, NRBB)                                                                                       \
+    LINA_LAUNCH((gla_decode_window_persist_kernel<DVV, NRBB, 1, TIO, TG, TS>), grid, dim3(256 * NRBB), 0, stream,      \
+                (const TIO*)q, (const TIO*)k, (const TIO*)v, (const TG*)gk, S, hk, hc, hv, step, origin, window, n_heads, \
+                H, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], scale, (const TIO*)gate, gate_sb, gate_sh,  \
+                (const TIO*)nw, eps, (TIO*)og, og_packed)
+#define LINA_WINP_CASE(DVV)                                                                                            \
+    case DVV:                                                                                                          \
+        if (Dk == 64) LINA_WINP_ONE(DVV, 1); else if (Dk == 128) LINA_WINP_ONE(DVV, 2);                                \
+        else if constexpr (sizeof(TIO) == 2) LINA_WINP_ONE(DVV, 4);                                                    \
+        break;
+    if (Dk != 64 && Dk != 128 && Dk != 256)
+        return fail(LINA_ERR_UNSUPPORTED, "lina_gla_decode_window_persist: Dk=%d not in {64,128,256}", Dk);
+    // 1024 threads leave 128 registers each: the raw fp32 q / k / v / gate of the next head do not fit beside the ring
+    if (Dk == 256 && sizeof(TIO) != 2)
+        return fail(LINA_ERR_UNSUPPORTED, "lina_gla_decode_window_persist: Dk=256 is built for bf16 activations (fp32: "
+                    "lina_gla_decode_window_s)");
+    switch (Dv) {
+        LINA_WINP_CASE(64) LINA_WINP_CASE(128) LINA_WINP_CASE(256)
+        default:
+            return fail(LINA_ERR_UNSUPPORTED, "lina_gla_decode_window_persist: Dv=%d not in {64,128,256} (Dv = 512 is served by "
+                        "lina_gla_decode_window_s)", Dv);
+    }
+#undef LINA_WINP_CASE
+#undef LINA_WINP_ONE
+    return check_launch("lina_gla_decode_window_persist");
 }
 
 }  // namespace lina
@@ -462,4 +785,43 @@ extern "C" int lina_gla_decode_window_flush_s(void* state, int state_dtype, cons
     return launch_window<bf16_t, float, bf16_t>(nullptr, nullptr, nullptr, nullptr, (bf16_t*)state, (float*)hist_k, (float*)hist_c,
                                                 (float*)hist_v, nullptr, nullptr, kWinMax, n_pending, B, H, Dk, Dv, st, 1.0f,
                                                 stream, nullptr, 0, 0, nullptr, 0.f, nullptr);
+}
+
+// ---- the persistent form (gla_decode_window_persist_kernel): the argument list of lina_gla_decode_window_s plus n_wg, the number
+// of workgroups (clamped to B * H); bit-identical results.  Dv <= 256 only.
+extern "C" int lina_gla_decode_window_persist(const void* q, const void* k, const void* v, const void* gk, void* state,
+                                              int state_dtype, const void* gate, const void* norm_weight, void* og,
+                                              float* o_exchange, int* counters,   // unused: Dv = 512 stays on the form above
+                                              float* hist_k, float* hist_c, float* hist_v, const int64_t* step,
+                                              const int64_t* origin, int window, int B, int H, int Dk, int Dv, int64_t q_sb,
+                                              int64_t q_sh, int64_t k_sb, int64_t k_sh, int64_t v_sb, int64_t v_sh,
+                                              int64_t g_sb, int64_t g_sh, int64_t gate_sb, int64_t gate_sh, float eps,
+                                              int og_packed, int dtype, int g_dtype, float scale, int n_wg,
+                                              lina_stream_t stream) {
+    using namespace lina;
+    LINA_REQUIRE(valid_dtype(state_dtype), "lina_gla_decode_window_persist: bad state dtype %d", state_dtype);
+    LINA_REQUIRE(q && k && v && gk && state && gate && norm_weight && og && hist_k && hist_c && hist_v && step && origin,
+                 "lina_gla_decode_window_persist: null pointer");
+    LINA_REQUIRE(B > 0 && H > 0, "lina_gla_decode_window_persist: B,H must be positive");
+    LINA_REQUIRE(n_wg >= 1, "lina_gla_decode_window_persist: n_wg must be at least 1 (got %d)", n_wg);
+    LINA_REQUIRE(window >= 1 && window <= kWinMax && (window & (window - 1)) == 0,
+                 "lina_gla_decode_window_persist: window must be a power of two in [1, %d]", kWinMax);
+    if (window > kWinPersist)
+        return fail(LINA_ERR_UNSUPPORTED, "lina_gla_decode_window_persist: window=%d > %d is served by lina_gla_decode_window_s", window, kWinPersist);
+    LINA_REQUIRE(valid_dtype(dtype) && valid_dtype(g_dtype), "lina_gla_decode_window_persist: bad dtype enum");
+    LINA_REQUIRE(gate_sb % 4 == 0 && gate_sh % 4 == 0, "lina_gla_decode_window_persist: gate strides must be multiples of 4");
+    const int64_t st[8] = {q_sb, q_sh, k_sb, k_sh, v_sb, v_sh, g_sb, g_sh};
+#define LINA_WINP_GO(TIO, TG, TS)                                                                                      \
+    return launch_window_persist<TIO, TG, TS>(q, k, v, gk, (TS*)state, hist_k, hist_c, hist_v, step, origin, window, n_wg, B, \
+                                              H, Dk, Dv, st, scale, stream, gate, gate_sb, gate_sh, norm_weight, eps, og, og_packed)
+    if (state_dtype == LINA_F32) {
+        if (dtype == LINA_F32 && g_dtype == LINA_F32) LINA_WINP_GO(float, float, float);
+        if (dtype == LINA_BF16 && g_dtype == LINA_F32) LINA_WINP_GO(bf16_t, float, float);
+        if (dtype == LINA_BF16 && g_dtype == LINA_BF16) LINA_WINP_GO(bf16_t, bf16_t, float);
+        return fail(LINA_ERR_UNSUPPORTED, "lina_gla_decode_window_persist: dtype=f32 with bf16 gates is not built");
+    }
+    if (dtype != LINA_BF16) return fail(LINA_ERR_UNSUPPORTED, "lina_gla_decode_window_persist: a bf16 state is built for bf16 activations");
+    if (g_dtype == LINA_F32) LINA_WINP_GO(bf16_t, float, bf16_t);
+    LINA_WINP_GO(bf16_t, bf16_t, bf16_t);
+#undef LINA_WINP_GO
 }

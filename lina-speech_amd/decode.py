@@ -218,8 +218,13 @@ class DecodeEngine:
                  window: Optional[int] = None, stream_weights=("in", "up"), cross: str = "spread",
                  fused_pick: bool = True, packed: bool = True, cross_tail_fused: bool = True,
                  share_weights_with: Optional["DecodeEngine"] = None, state_dtype: Optional[torch.dtype] = None,
-                 x_lens=None):
-        """``x_lens`` (B ints, 1 <= L_b <= Ttxt): the rows' texts are right-padded to x_enc's width and row b's ends at L_b --
+                 x_lens=None, k1w_persist_wg: Optional[int] = None):
+        """``k1w_persist_wg``: workgroups of the persistent K1w of the lazy step (0 = one workgroup per head; default:
+        ``POLICY.k1w_persist_wg``, inside a DecodeEngineGroup of two engines of >= 192 rows ``POLICY.k1w_persist_wg_group``).
+        It applies where the persistent form is built AND was measured -- bf16 activations, Dv <= 256, window <= 8; an engine
+        with fp32 activations, Dv = 512 or window 16 runs the one-workgroup-per-head kernel whatever this says (a choice of
+        the engine; the operator itself, ``ops.gla_decode_window(n_wg=...)``, raises for a shape it does not serve).
+        ``x_lens`` (B ints, 1 <= L_b <= Ttxt): the rows' texts are right-padded to x_enc's width and row b's ends at L_b --
         the cross-attention of row b then runs over its own L_b positions with a positional table of its own (the ragged
         launches of the default step; ``cross="fused"`` and ``cross_tail_fused=False`` take no lengths).  ``x_enc`` must come
         from the text encoder run with the matching mask (LinaModel.generate_batch(x_lens=...) does that).
@@ -249,6 +254,7 @@ class DecodeEngine:
         rnn = model.attentive_rnn
         self.model = model
         self.fuse_norm = fuse_norm
+        self.k1w_persist_wg = ops.POLICY.k1w_persist_wg if k1w_persist_wg is None else int(k1w_persist_wg)
         self.B = batch_size
         self.dev = x_enc.device
         if state_dtype not in (None, torch.float32, torch.bfloat16):
@@ -381,9 +387,13 @@ class DecodeEngine:
             pass                                  # measurement only (time_update_kernel): the step without K1w / K1d
         elif (lazy and P.lazy) or P.S.dtype == torch.bfloat16:
             # (a bf16 state outside the device loop: the same kernel as an immediate update, window 1)
+            win = P.window if lazy else 1
+            # the persistent form where the policy asks for it and the form serves the shape (Dv = 512, window 16: the
+            # one-workgroup-per-head kernel)
+            n_wg = self.k1w_persist_wg if (lazy and P.Dv <= 256 and win <= 8 and q.dtype == torch.bfloat16) else 0
             ops.gla_decode_window(q, k, v, P.gk.view(B, P.H, P.Dk), P.S, gate, P.gnw, P.og_p if packed else P.og,
-                                  P.hk, P.hc, P.hv, self._t_idx, self._origin, P.window if lazy else 1, P.eps_gate,
-                                  og_packed=packed, o_exchange=P.o_x, counters=P.counters)
+                                  P.hk, P.hc, P.hv, self._t_idx, self._origin, win, P.eps_gate,
+                                  og_packed=packed, o_exchange=P.o_x, counters=P.counters, n_wg=n_wg)
         elif P.row_split and self.fuse_norm:
             ops.gla_decode_update_norm(q, k, v, P.gk.view(B, P.H, P.Dk), P.o_part, P.S, gate, P.gnw, P.og,
                                        P.counters, P.eps_gate)
@@ -1014,6 +1024,10 @@ class DecodeEngineGroup:
         self.ranges = [shard_rows(batch_size, i, n_engines) for i in range(n_engines)]
         lens = None if x_lens is None else text_lengths(x_lens, batch_size, x_enc.shape[1])   # (each engine: its slice)
         self.engines = []
+        # the group's K1w grid where it was measured (two engines of 192 rows or more, profiles/k1w_persist_sweep.txt);
+        # any other group keeps the one-workgroup-per-head kernel
+        measured = n_engines == 2 and min(hi - lo for lo, hi in self.ranges) >= ops.POLICY.K1W_PERSIST_GROUP_MIN_ROWS
+        engine_args.setdefault("k1w_persist_wg", ops.POLICY.k1w_persist_wg_group if measured else 0)
         for lo, hi in self.ranges:
             xe = x_enc[lo:hi] if x_enc.shape[0] == batch_size else x_enc
             self.engines.append(DecodeEngine(model, xe, batch_size=hi - lo, x_lens=None if lens is None else lens[lo:hi],

@@ -26,6 +26,16 @@ class Policy:
     # train path, channel mixer: the down-projection's operand in rows of 1536 (not 1408) elements so that its dX GEMM
     # ([M, 1024] x [1024, 1536]: 90-100 us; x [1024, 1408]: 112-119) runs on the width the GEMM library prefers
     wide_down_dx: bool = True
+    # decode, K1w: workgroups of the PERSISTENT form (lina_gla_decode_window_persist) -- 0 = the one-workgroup-per-head kernel.
+    # ``k1w_persist_wg``: an engine on its own -- 0: a grid of 256 measured +2.6 % at 512 rows and +1.7 % at 256, inside the
+    # 4.5 % two boxes differ by, and -3 % at 64 rows; any smaller grid is slower.  ``k1w_persist_wg_group``: an engine of a
+    # DecodeEngineGroup, where a grid below the chip's 256 CUs leaves CUs to the other engine's projection chain: 2 x 256
+    # rows 2.130 -> 2.033 ms per token at 192 (160: 2.050, 224: 2.121, 256: 2.153); across boxes +2.4 ... +6.3 % over the plain
+    # kernel; 2 x 192 rows 1.695 -> 1.665.  Applied by DecodeEngineGroup to two engines of >= K1W_PERSIST_GROUP_MIN_ROWS rows
+    # only: nothing else was measured.  profiles/k1w_persist_sweep.txt, k1w_persist_after.txt.
+    k1w_persist_wg: int = 0
+    k1w_persist_wg_group: int = 192
+    K1W_PERSIST_GROUP_MIN_ROWS = 192      # rows per engine from which the group value applies (two engines; measured at 192 and 256)
 
 
 POLICY = Policy()
