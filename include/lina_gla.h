@@ -226,6 +226,19 @@ int lina_sample_pick_embed(const void* logits, int64_t row_stride, const void* t
                            int L, int n_emb, int d, int max_steps, int n_sampled, int k, float temp, uint64_t seed,
                            int dtype, lina_stream_t stream);
 
+/* K6f -- K6d / K6e with a per-row FORCED next input: codec prompts of different lengths in one batch (the reference's
+ * `if exists(prompt) and t < p_len: y_embd = prompt[:, [t]]`, model/modeling_lina.py:175, with a p_len per row).  Everything
+ * is lina_sample_pick_embed (n_sampled = 0: all quantizers greedy, the picks of lina_greedy_pick_embed) -- picks, draws from
+ * (seed, step[0], b*Q + q), token log, loop_ctl, step[0] += 1 all come from the picks -- except the embedding written to
+ * x_out[b,:] (and x_out_packed): with t = step[0], while 0 <= t < force_len[b] and t < P_cap it is
+ * sum_q table[q, force_tok[t][q][b], :] (ids clamped to [0, n_emb) as K6a does; bit-equal to lina_embed_sum), else that of
+ * the picks.   force_tok: int64 [P_cap][Q][B] (step-major, like tok_log);  force_len: int32 [B] (0 = row never forced);
+ * t >= P_cap is "not forced", so force_tok is never read out of range.  Both are required (null: LINA_ERR_ARG). */
+int lina_pick_embed_forced(const void* logits, int64_t row_stride, const void* table, void* x_out,
+                           void* x_out_packed, int64_t* tok_log, int64_t* step, int* counter, int* loop_ctl, int B, int Q,
+                           int L, int n_emb, int d, int max_steps, int n_sampled, int k, float temp, uint64_t seed,
+                           const int64_t* force_tok, const int* force_len, int P_cap, int dtype, lina_stream_t stream);
+
 /* K6b -- greedy pick: out[r] = argmax_j logits[r,j], lowest index on exact ties.
  * Replaces topk_sampling(k=1) (reference model/tools.py:38-44, modeling_lina.py:159-164);
  * identical except on exact ties, where the reference draws uniformly among them. */

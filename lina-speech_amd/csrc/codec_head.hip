@@ -64,6 +64,28 @@ __device__ __forceinline__ void note_stop(int* ctl, const int* toks, int Q, int 
     if (ticket_agent(ctl + kCtlCount) == B - 1) ctl[kCtlStopAt] = (int)t;   // this row was the last one still running
 }
 
+// The next step's input of row b, x_out[b,:] = sum_q table[q, toks[q], :] (K6a's order and precision: bit-equal to
+// lina_embed_sum on the same tokens), row-major and -- with x_pk -- fragment-major.  toks: Q non-negative ids in LDS.
+template <typename T>
+__device__ __forceinline__ void embed_row(const int* toks, const T* __restrict__ table, T* __restrict__ x_out,
+                                          T* __restrict__ x_pk, int b, int Q, int n_emb, int d) {
+    for (int e = threadIdx.x * 4; e < d; e += 256 * 4) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int qi = 0; qi < Q; ++qi) {
+            int tok = toks[qi];
+            tok = tok >= n_emb ? n_emb - 1 : tok;
+            const float4 r = ld4(table + ((int64_t)qi * n_emb + tok) * d + e);
+            acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
+        }
+        st4(x_out + (int64_t)b * d + e, acc);
+        if (x_pk) {                                  // fragment-major copy (the model-dtype values just stored)
+            T tmp4[4];
+            st4(tmp4, acc);
+            st4(x_pk + packed_off<T>(b, e, d), ld4(tmp4));
+        }
+    }
+}
+
 // K6d -- the whole token epilogue of a greedy decode step in ONE launch (one workgroup per batch row): arg-max of every
 // quantizer's logits (K6b), the pick appended to the device-side token log at position step[0], the next step's input
 // embedding sum_q table[q, pick_q] (K6a) written into the residual-stream buffer, and -- by the LAST workgroup to finish,
@@ -106,21 +128,7 @@ __global__ __launch_bounds__(256) void greedy_pick_embed_kernel(const T* __restr
         }
     }
     __syncthreads();
-    for (int e = tid * 4; e < d; e += 256 * 4) {
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int qi = 0; qi < Q; ++qi) {
-            int tok = s_tok[qi];
-            tok = tok >= n_emb ? n_emb - 1 : tok;
-            const float4 r = ld4(table + ((int64_t)qi * n_emb + tok) * d + e);
-            acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
-        }
-        st4(x_out + (int64_t)b * d + e, acc);
-        if (x_pk) {                                  // fragment-major copy (the model-dtype values just stored)
-            T tmp4[4];
-            st4(tmp4, acc);
-            st4(x_pk + packed_off<T>(b, e, d), ld4(tmp4));
-        }
-    }
+    embed_row(s_tok, table, x_out, x_pk, b, Q, n_emb, d);
     if (tid == 0) {
         if (ctl) note_stop(ctl, s_tok, Q, b, B, s_step);
         const int tk = ticket_agent(counter);       // taken AFTER this workgroup has read step[0]
@@ -136,13 +144,19 @@ __global__ __launch_bounds__(256) void greedy_pick_embed_kernel(const T* __restr
 // launch like K6d: per batch row the Q picks (K6c on the sampled quantizers with the uniform number of row b*Q + q of a
 // [B*Q]-row lina_topk_sample_rows call at the same (seed, step) -- the tokens are the ones the separate launches give --,
 // K6b on the others), the token log, the next-input embedding (row-major and, optionally, fragment-major) and step[0] += 1.
-template <typename T>
+//
+// kForced (lina_pick_embed_forced, the codec prompts of different lengths of one batch): row b's next input at step t is the
+// embedding of force_tok[t][.][b] (int64 [P_cap][Q][B], step-major like tok_log) while 0 <= t < min(force_len[b], P_cap) -- the
+// picks, their draws, the token log, the stop bookkeeping and the step counter are those of the unforced kernel.
+template <typename T, bool kForced>
 __global__ __launch_bounds__(256) void sample_pick_embed_kernel(const T* __restrict__ logits, int64_t row_stride,
                                                                 const T* __restrict__ table, T* __restrict__ x_out,
                                                                 int64_t* __restrict__ tok_log, int64_t* step, int* counter,
                                                                 int Q, int L, int n_emb, int d, int max_steps,
                                                                 T* __restrict__ x_pk, int n_sampled, int k, float inv_temp,
-                                                                uint64_t seed, int* ctl) {
+                                                                uint64_t seed, int* ctl,
+                                                                const int64_t* __restrict__ force_tok,
+                                                                const int* __restrict__ force_len, int P_cap) {
     LINA_DYN_SMEM(smem_raw);
     float* s_x = reinterpret_cast<float*>(smem_raw);            // [L] the row being sampled
     __shared__ SampleScratch sc;
@@ -172,21 +186,23 @@ __global__ __launch_bounds__(256) void sample_pick_embed_kernel(const T* __restr
         }
     }
     __syncthreads();
-    for (int e = tid * 4; e < d; e += 256 * 4) {
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int qi = 0; qi < Q; ++qi) {
-            int tok = s_tok[qi];
-            tok = tok >= n_emb ? n_emb - 1 : tok;
-            const float4 r = ld4(table + ((int64_t)qi * n_emb + tok) * d + e);
-            acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
+    const int* in_tok = s_tok;
+    if constexpr (kForced) {
+        // the reference's `if exists(prompt) and t < p_len: y_embd = prompt[:, [t]]` (model/modeling_lina.py:175) per row: the
+        // picks above stay what is logged and what the stop flags see, only the next input is the row's prompt token
+        __shared__ int s_in[16];
+        if (tid < Q) {
+            int tok = s_tok[tid];
+            if (t >= 0 && t < P_cap && t < force_len[b]) {
+                const int64_t f = force_tok[(t * Q + tid) * B + b];
+                tok = (int)(f < 0 ? 0 : (f >= n_emb ? n_emb - 1 : f));   // K6a's clamp: never read out of bounds
+            }
+            s_in[tid] = tok;
         }
-        st4(x_out + (int64_t)b * d + e, acc);
-        if (x_pk) {                                  // fragment-major copy (the model-dtype values just stored)
-            T tmp4[4];
-            st4(tmp4, acc);
-            st4(x_pk + packed_off<T>(b, e, d), ld4(tmp4));
-        }
+        __syncthreads();
+        in_tok = s_in;
     }
+    embed_row(in_tok, table, x_out, x_pk, b, Q, n_emb, d);
     if (tid == 0) {
         if (ctl) note_stop(ctl, s_tok, Q, b, B, t);
         const int tk = ticket_agent(counter);       // taken AFTER this workgroup has read step[0]
@@ -238,14 +254,46 @@ extern "C" int lina_sample_pick_embed(const void* logits, int64_t row_stride, co
     dim3 grid((unsigned)B);
     const size_t smem = n_sampled > 0 ? (size_t)L * sizeof(float) : 0;
     if (dtype == LINA_F32)
-        LINA_LAUNCH((sample_pick_embed_kernel<float>), grid, dim3(256), smem, stream, (const float*)logits, row_stride,
+        LINA_LAUNCH((sample_pick_embed_kernel<float, false>), grid, dim3(256), smem, stream, (const float*)logits, row_stride,
                     (const float*)table, (float*)x_out, tok_log, step, counter, Q, L, n_emb, d, max_steps,
-                    (float*)x_out_packed, n_sampled, k, 1.0f / temp, seed, loop_ctl);
+                    (float*)x_out_packed, n_sampled, k, 1.0f / temp, seed, loop_ctl, (const int64_t*)nullptr,
+                    (const int*)nullptr, 0);
     else
-        LINA_LAUNCH((sample_pick_embed_kernel<bf16_t>), grid, dim3(256), smem, stream, (const bf16_t*)logits, row_stride,
+        LINA_LAUNCH((sample_pick_embed_kernel<bf16_t, false>), grid, dim3(256), smem, stream, (const bf16_t*)logits, row_stride,
                     (const bf16_t*)table, (bf16_t*)x_out, tok_log, step, counter, Q, L, n_emb, d, max_steps,
-                    (bf16_t*)x_out_packed, n_sampled, k, 1.0f / temp, seed, loop_ctl);
+                    (bf16_t*)x_out_packed, n_sampled, k, 1.0f / temp, seed, loop_ctl, (const int64_t*)nullptr,
+                    (const int*)nullptr, 0);
     return check_launch("lina_sample_pick_embed");
+}
+
+extern "C" int lina_pick_embed_forced(const void* logits, int64_t row_stride, const void* table, void* x_out,
+                                      void* x_out_packed, int64_t* tok_log, int64_t* step, int* counter, int* loop_ctl, int B,
+                                      int Q, int L, int n_emb, int d, int max_steps, int n_sampled, int k, float temp,
+                                      uint64_t seed, const int64_t* force_tok, const int* force_len, int P_cap, int dtype,
+                                      lina_stream_t stream) {
+    using namespace lina;
+    LINA_REQUIRE(logits && table && x_out && tok_log && step && counter, "lina_pick_embed_forced: null pointer");
+    LINA_REQUIRE(force_tok && force_len, "lina_pick_embed_forced: null force_tok / force_len");
+    LINA_REQUIRE(B > 0 && Q > 0 && Q <= 16 && L > 0 && n_emb > 0 && max_steps > 0,
+                 "lina_pick_embed_forced: B,Q (<= 16),L,n_emb,max_steps must be positive");
+    LINA_REQUIRE(P_cap > 0, "lina_pick_embed_forced: P_cap=%d must be positive", P_cap);
+    LINA_REQUIRE(d > 0 && d % 4 == 0, "lina_pick_embed_forced: d=%d must be a positive multiple of 4", d);
+    LINA_REQUIRE(n_sampled >= 0 && n_sampled <= Q, "lina_pick_embed_forced: n_sampled must be in [0, Q]");
+    LINA_REQUIRE(k >= 1 && temp > 0.0f, "lina_pick_embed_forced: k must be >= 1 and temp positive");
+    LINA_REQUIRE(valid_dtype(dtype), "lina_pick_embed_forced: bad dtype %d", dtype);
+    LINA_REQUIRE(!x_out_packed || d % (dtype == LINA_BF16 ? 32 : 16) == 0, "lina_pick_embed_forced: packed copy needs whole k-steps");
+    if (L > kSampleMaxN) return fail(LINA_ERR_UNSUPPORTED, "lina_pick_embed_forced: L=%d exceeds %d", L, kSampleMaxN);
+    dim3 grid((unsigned)B);
+    const size_t smem = n_sampled > 0 ? (size_t)L * sizeof(float) : 0;
+    if (dtype == LINA_F32)
+        LINA_LAUNCH((sample_pick_embed_kernel<float, true>), grid, dim3(256), smem, stream, (const float*)logits, row_stride,
+                    (const float*)table, (float*)x_out, tok_log, step, counter, Q, L, n_emb, d, max_steps,
+                    (float*)x_out_packed, n_sampled, k, 1.0f / temp, seed, loop_ctl, force_tok, force_len, P_cap);
+    else
+        LINA_LAUNCH((sample_pick_embed_kernel<bf16_t, true>), grid, dim3(256), smem, stream, (const bf16_t*)logits, row_stride,
+                    (const bf16_t*)table, (bf16_t*)x_out, tok_log, step, counter, Q, L, n_emb, d, max_steps,
+                    (bf16_t*)x_out_packed, n_sampled, k, 1.0f / temp, seed, loop_ctl, force_tok, force_len, P_cap);
+    return check_launch("lina_pick_embed_forced");
 }
 
 extern "C" int lina_embed_sum(const int64_t* idx, const void* table, void* out, int Q, int64_t N, int n_emb, int d,

@@ -171,6 +171,18 @@ class _BlockPack:
             self.hv = torch.zeros(self.window, B * self.H, self.Dv, dtype=torch.float32, device=dev)
 
 
+def prompt_lengths(prompt_lens, B: int, P: int) -> list:
+    """``prompt_lens`` (LongTensor or sequence of B ints) -> list of ints, each in [0, P]; ValueError otherwise."""
+    if isinstance(prompt_lens, torch.Tensor) and prompt_lens.dim() != 1:
+        raise ValueError("prompt_lens must be 1-D: one prompt length per row")
+    lens = prompt_lens.tolist() if isinstance(prompt_lens, torch.Tensor) else list(prompt_lens)
+    if len(lens) != B:
+        raise ValueError(f"prompt_lens has {len(lens)} entries for {B} rows")
+    if any(int(p) != p or not 0 <= int(p) <= P for p in lens):
+        raise ValueError(f"every prompt length must be an integer in [0, {P}] (the padded prompt width)")
+    return [int(p) for p in lens]
+
+
 def text_lengths(x_lens, B: int, Tn: int) -> list:
     """``x_lens`` (LongTensor or sequence of B ints) -> list of ints, each in [1, Tn]; ValueError otherwise."""
     if isinstance(x_lens, torch.Tensor) and x_lens.dim() != 1:
@@ -205,10 +217,13 @@ class _Part:
 
 class _Loop:
     """One captured configuration of the device-side decode loop: its logs, control block and hipGraphs."""
-    __slots__ = ("cap", "tok_log", "att_log", "att_direct", "ctl", "body", "graph1", "graphN", "att", "hid_log")
+    __slots__ = ("cap", "tok_log", "att_log", "att_direct", "ctl", "body", "graph1", "graphN", "att", "hid_log",
+                 "forced", "p_cap", "force_tok", "force_len")
 
     def __init__(self):
         self.cap, self.tok_log, self.att_log, self.att_direct, self.ctl, self.hid_log = 0, None, None, False, None, None
+        # a forced loop (codec prompts of different lengths): the static operands of K6f its graphs point at
+        self.forced, self.p_cap, self.force_tok, self.force_len = False, 0, None, None
         self.body = self.graph1 = self.graphN = self.att = None
 
 
@@ -628,7 +643,7 @@ class DecodeEngine:
     # ------------------------------------------------------------------ fully device-side decode loop
     def begin_greedy(self, max_steps: int, y0: Optional[torch.Tensor] = None, k: int = 1, temp: float = 1.0,
                      seed: int = 0, first_greedy_quant: int = 0, log_att: bool = False, t0: int = 0,
-                     log_hidden: bool = False):
+                     log_hidden: bool = False, forced=None):
         """Arm the device-side decode loop: token picks, the stop bookkeeping, the next-token embedding (K6a), the token
         log and -- with ``log_att`` -- the attention log are part of the captured step, so one token == one graph replay
         and nothing is read back until ``greedy_tokens()``.  Quantizers ``i < first_greedy_quant`` are SAMPLED (top-``k``,
@@ -639,6 +654,12 @@ class DecodeEngine:
         recurrent-state error where the logits of a peaked head are dominated by the embedding -> head shortcut.
         ``t0``: the step index the loop starts at (a prompt prefill has produced steps 0 .. t0-1; ``preload``
         puts their tokens / attention rows into the logs).  The recurrent state is NOT reset (``reset()`` does that).
+        ``forced`` = (tokens [Q,B,P] int64, lens [B], 0 <= lens[b] <= P): codec prompts of different lengths -- at step t
+        (an ABSOLUTE index: with ``t0`` > 0 the loop reads tokens[:, :, t0:]) row b's next input is the embedding of
+        tokens[:, b, t] while t < lens[b] and that of its picks afterwards (the reference's ``t < p_len`` rule,
+        modeling_lina.py:175, per row; K6f).  The picks, the token log and the stop flags are the loop's own either way.
+        A forced loop is a configuration of its own (its graphs point at its static token / length buffers, which arming
+        rewrites in place); the loops captured without ``forced`` are the ones they were.
 
         A configuration (sampling mode, att log, operand layout) is captured ONCE per engine and kept (``self._loops``):
         arming it again only rewrites the control block (stop flags, per-call seed word), the step counters and the
@@ -657,10 +678,16 @@ class DecodeEngine:
                   and all(P.packed for P in self.packs) and self._packed_ok)
         if n_sampled == 0:
             k, temp = 1, 1.0
+        f_tok = f_len = None
+        if forced is not None:
+            f_tok, f_len = forced
+            if f_tok.dim() != 3 or f_tok.shape[0] != self.Q or f_tok.shape[1] != self.B or f_tok.dtype != torch.long:
+                raise ValueError(f"forced tokens must be an int64 [Q, B, P] = [{self.Q}, {self.B}, P] tensor")
+            f_len = prompt_lengths(f_len, self.B, f_tok.shape[2])
         key = (n_sampled, int(k), float(temp), bool(log_att), packed, fused_pick, 0 if fused_pick else int(seed),
-               bool(log_hidden))
+               bool(log_hidden), forced is not None)
         loop = self._loops.pop(key, None)
-        if loop is None or loop.cap < max_steps:
+        if loop is None or loop.cap < max_steps or (forced is not None and loop.p_cap < f_tok.shape[2]):
             # a configuration owns its logs (att log: B x 2 x cap x T_txt, ~134 MB at B = 512) and two hipGraphs; callers that
             # sweep k / temp (captured kernel arguments) or, on the unfused pick path, the seed would otherwise grow the set
             # without bound: keep the MAX_LOOPS most recently used (dropped here, outside any stream capture)
@@ -668,7 +695,7 @@ class DecodeEngine:
                 self._drop_loop(loop)                        # (too short: rebuilt with longer logs)
             while len(self._loops) >= self.MAX_LOOPS:
                 self._drop_loop(self._loops.pop(next(iter(self._loops))))
-            loop = self._build_loop(key, max_steps, lazy)
+            loop = self._build_loop(key, max_steps, lazy, 0 if forced is None else f_tok.shape[2])
         self._loops[key] = loop                              # most recently used last
         self._loop = loop
         self._loop_packed = packed
@@ -677,6 +704,10 @@ class DecodeEngine:
         loop.tok_log.zero_()
         loop.ctl.copy_(ops.new_loop_ctl(self.B, "cpu", int(seed) if fused_pick else 0))
         self._pick_counter.zero_()
+        if forced is not None:                               # in place: the captured launches know the addresses
+            loop.force_tok.zero_()
+            loop.force_tok[:f_tok.shape[2]].copy_(f_tok.permute(2, 0, 1))
+            loop.force_len.copy_(torch.tensor(f_len, dtype=torch.int32))
         self._t_idx.fill_(t0)
         self._origin.fill_(t0)
         self._n_done, self._origin_host, self._t0 = t0, t0, t0
@@ -689,13 +720,17 @@ class DecodeEngine:
         """One row range: the residual-stream buffer itself is the step's input (no y -> x copy, no embed -> y copy)."""
         return self.parts[0].x if len(self.parts) == 1 else self._y_in
 
-    def _build_loop(self, key, max_steps: int, lazy: bool):
-        n_sampled, k, temp, log_att, packed, fused_pick, seed, log_hidden = key
+    def _build_loop(self, key, max_steps: int, lazy: bool, p_max: int = 0):
+        n_sampled, k, temp, log_att, packed, fused_pick, seed, log_hidden, forced = key
         emb = self.model.rvq_embed
         L = _Loop()
         L.cap = (max(int(max_steps), 1) + 63) // 64 * 64
         L.tok_log = torch.zeros(L.cap, self.Q, self.B, dtype=torch.long, device=self.dev)
         L.ctl = ops.new_loop_ctl(self.B, self.dev)
+        if forced:                                           # P_cap rounded up like cap: other prompts re-arm this loop
+            L.forced, L.p_cap = True, (max(int(p_max), 1) + 63) // 64 * 64
+            L.force_tok = torch.zeros(L.p_cap, self.Q, self.B, dtype=torch.long, device=self.dev)
+            L.force_len = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
         hw_dt = self._att.dtype
         L.att_log = torch.zeros(self.B, 2, L.cap, self.Tn, dtype=hw_dt, device=self.dev) if log_att else None
         # the two cross-attention launches of the default step write their rows straight into the log at the device step
@@ -721,6 +756,12 @@ class DecodeEngine:
             if L.hid_log is not None:          # before the token epilogue overwrites the stream with the next token's embedding
                 L.hid_log.index_copy_(0, self._t_idx, (self.parts[0].x_p if packed else self.parts[0].x).reshape(1, -1))
             lg = logits.view(self.B, self.Q, self.L)
+            if forced and fused_pick:
+                # K6f: K6d / K6e with the next input of the rows still inside their prompt taken from force_tok
+                ops.pick_embed_forced(lg, emb.weight, y_buf, L.tok_log, self._t_idx, self._pick_counter, L.force_tok,
+                                      L.force_len, n_sampled, k, temp, seed=0,
+                                      x_packed=self.parts[0].x_p if packed else None, loop_ctl=L.ctl)
+                return att
             if n_sampled == 0 and self.Q <= 16:
                 # K6d: picks, token log, stop flags, next-token embedding and the step counter in ONE launch
                 ops.greedy_pick_embed(lg, emb.weight, y_buf, L.tok_log, self._t_idx, self._pick_counter,
@@ -746,6 +787,10 @@ class DecodeEngine:
             L.ctl[0:1].copy_(rows.sum().to(torch.int32).view(1))
             first = (L.ctl[0:1] >= self.B) & (L.ctl[1:2] < 0)
             L.ctl[1:2].copy_(torch.where(first, self._t_idx.to(torch.int32), L.ctl[1:2]))
+            if forced:       # the same rule as K6f: the picks are logged, the rows inside their prompt are fed its token
+                inside = (self._t_idx < L.force_len) & (self._t_idx < L.p_cap)                    # [B]
+                pick = torch.where(inside.unsqueeze(0), L.force_tok.index_select(0, self._t_idx.clamp(max=L.p_cap - 1))[0],
+                                   pick)
             self._t_idx.add_(1)
             ops.embed_sum(emb.weight, pick, out=y_buf)              # next step's input, written in place
             return att
@@ -783,6 +828,7 @@ class DecodeEngine:
         """A loop's body closes over the loop object (a reference cycle): cut it, so that its logs and hipGraphs go NOW -- outside
         any stream capture -- and not whenever the cyclic collector runs."""
         L.body = L.graph1 = L.graphN = L.att = L.tok_log = L.att_log = L.ctl = L.hid_log = None
+        L.force_tok = L.force_len = None
 
     def close(self):
         """Release the engine's device memory and hipGraphs now.  An engine is a reference cycle (its loop bodies close over
@@ -923,18 +969,19 @@ class DecodeEngine:
     @torch.inference_mode()
     def generate(self, max_seqlen: int, y0: Optional[torch.Tensor] = None, k: int = 1, temp: float = 1.0,
                  first_greedy_quant: int = 0, seed: int = 0, force_max_seqlen: bool = False,
-                 stop_check_every: int = 16, log_att: bool = True, preload=None):
+                 stop_check_every: int = 16, log_att: bool = True, preload=None, forced=None):
         """The loop of the reference's ``generate_batch`` (model/modeling_lina.py:152-179) on the device: up to
         ``max_seqlen`` steps in replays of GRAPH_STEPS tokens; every ``stop_check_every`` steps 8 bytes of the control
         block are copied to pinned host memory BEHIND the queued work, and the copy issued one check earlier is looked at
         -- the GPU always has the next group of steps queued, the host never waits for the step it has just enqueued.
         When the block says that every row has stopped, the loop ends; up to two groups of steps may have run past that
         point, and the logs are trimmed to the exact length the reference's per-step check produces.
-        ``preload`` = (tokens [Q,B,t0], atts [B,2,t0,Ttxt]) of a prompt prefill.  Returns (qs [Q,B,n], atts [B,2,n,Ttxt]
+        ``preload`` = (tokens [Q,B,t0], atts [B,2,t0,Ttxt]) of a prompt prefill; ``forced`` = (tokens [Q,B,P], lens [B]): codec
+        prompts of different lengths, fed per row by the loop itself (begin_greedy).  Returns (qs [Q,B,n], atts [B,2,n,Ttxt]
         or None, n)."""
         t0 = 0 if preload is None else int(preload[0].shape[2])
         self.begin_greedy(max_seqlen, y0, k=k, temp=temp, seed=seed, first_greedy_quant=first_greedy_quant,
-                          log_att=log_att, t0=t0)
+                          log_att=log_att, t0=t0, forced=forced)
         if preload is not None:
             self.preload(*preload)
         L = self._loop

@@ -338,6 +338,40 @@ def sample_pick_embed(logits, table, x_out, tok_log, step, counter, n_sampled: i
                                          int(seed) & 0xFFFFFFFFFFFFFFFF, _dt(table), be.stream(table)))
 
 
+def pick_embed_forced(logits, table, x_out, tok_log, step, counter, force_tok, force_len, n_sampled: int = 0, k: int = 1,
+                      temp: float = 1.0, seed: int = 0, x_packed=None, loop_ctl=None):
+    """K6f (lina_pick_embed_forced): sample_pick_embed (``n_sampled = 0``: greedy_pick_embed) whose next input is FORCED per
+    row -- with t = step[0], ``x_out[b] = sum_q table[q, force_tok[t, q, b]]`` while ``t < force_len[b]`` (and t < P_cap), the
+    embedding of the picks otherwise; picks, token log, stop bookkeeping and ``step[0] += 1`` do not depend on it.
+    ``force_tok``: int64 [P_cap, Q, B] contiguous; ``force_len``: int32 [B]."""
+    be = _backend._BACKEND
+    be.require(logits, table, x_out, tok_log, step, counter, x_packed, force_tok, force_len)
+    B, Q, L = logits.shape
+    Qt, n_emb, d = table.shape
+    if Qt != Q or logits.stride(2) != 1 or logits.stride(1) != L:
+        raise ValueError("logits must be [B, Q, L] with contiguous (Q, L)")
+    if tuple(x_out.shape) != (B, d) or not x_out.is_contiguous() or x_out.dtype != table.dtype or logits.dtype != table.dtype:
+        raise ValueError("x_out must be a contiguous [B, d] tensor of the table's dtype")
+    if tok_log.dtype != torch.int64 or tok_log.dim() != 3 or tuple(tok_log.shape[1:]) != (Q, B) or not tok_log.is_contiguous():
+        raise ValueError("tok_log must be a contiguous int64 [max_steps, Q, B] tensor")
+    if step.dtype != torch.int64 or counter.dtype != torch.int32:
+        raise ValueError("step must be int64, counter int32")
+    if x_packed is not None and x_packed.numel() < packed_numel(B, d):
+        raise ValueError("packed x buffer is too small")
+    if (force_tok is None or force_tok.dtype != torch.int64 or force_tok.dim() != 3 or force_tok.shape[0] < 1
+            or tuple(force_tok.shape[1:]) != (Q, B) or not force_tok.is_contiguous()):
+        raise ValueError("force_tok must be a contiguous int64 [P_cap, Q, B] tensor")
+    if (force_len is None or force_len.dtype != torch.int32 or tuple(force_len.shape) != (B,)
+            or not force_len.is_contiguous()):
+        raise ValueError("force_len must be a contiguous int32 [B] tensor")
+    _check(be.lib.lina_pick_embed_forced(_ptr(logits), logits.stride(0), _ptr(table.contiguous()), _ptr(x_out),
+                                         _ptr(x_packed), _ptr(tok_log), _ptr(step), _ptr(counter),
+                                         _loop_ctl_ptr(be, loop_ctl, B), B, Q, L, n_emb, d,
+                                         tok_log.shape[0], int(n_sampled), int(k), float(temp),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(force_tok), _ptr(force_len),
+                                         force_tok.shape[0], _dt(table), be.stream(table)))
+
+
 # --------------------------------------------------------------------------- decode-step fusions
 def topk_sample_rows(logits, k: int, temp: float = 1.0, u: Optional[torch.Tensor] = None, seed: int = 0,
                      step: Optional[torch.Tensor] = None, out=None):

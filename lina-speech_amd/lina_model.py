@@ -156,7 +156,7 @@ class LinaModel(nn.Module):
                        max_seqlen: int = 1000, k: int = 100, first_greedy_quant: int = 1, temp: float = 1.0,
                        init_state=None, force_max_seqlen: bool = False, stop_check_every: int = 16,
                        engine: Optional[str] = None, seed: Optional[int] = None, n_engines: Optional[int] = None,
-                       state_dtype: Optional[torch.dtype] = None, *, x_lens=None):
+                       state_dtype: Optional[torch.dtype] = None, *, x_lens=None, prompt_lens=None):
         """Reference model/modeling_lina.py:111-192 (same arguments, same four returns).  ``engine``:
           None / "auto" -- the device-side loop (decode.DecodeEngine.generate: one hipGraph replay per 8 tokens, picks /
                            stop flags / attention log / next-token embedding inside the graph) when the architecture is
@@ -177,8 +177,19 @@ class LinaModel(nn.Module):
         (padded with 0 here, lengths derived; ``batch_size`` must equal len(x)).  Row i then decodes as
         ``generate_batch(x[i, :x_lens[i]], batch_size=1)`` would: the text encoder masks the padding, both attentions of the
         cross-attention run over the row's own positions with a positional table at its own width, the attention log holds
-        zeros at the padding and row i's cut is trimmed to its text.  All lengths == Tmax: the uniform path, unchanged."""
+        zeros at the padding and row i's cut is trimmed to its text.  All lengths == Tmax: the uniform path, unchanged.
+        ``prompt_lens`` (keyword only; ours): codec prompts of different lengths in one batch -- ``prompt`` [Q, B, P]
+        right-padded and row i's excerpt ends at ``prompt_lens[i]`` (0 <= prompt_lens[i] <= P, 0 = no prompt; LongTensor or
+        list).  ``prompt`` may also be a list of B tensors [Q, p_i] (padded here, lengths derived; ``batch_size`` must equal
+        len(prompt)).  Row i then decodes as ``generate_batch(x_i, batch_size=1, prompt=prompt[:, i:i+1, :p_i])`` would: the
+        reference's ``t < p_len`` rule (modeling_lina.py:175) with the row's own p_len.  The min(prompt_lens) + 1 positions
+        common to every row go through the one-pass prefill; from there the loop feeds each row its prompt token while it has
+        one (K6f on the device loop, ``torch.where`` on the other paths).  All lengths == P: the uniform path, unchanged.  No
+        speaker encoder (the reference's reads the first frames of the prompt with no mask)."""
         B, Q = batch_size, self.n_quant
+        prompt, p_lens = self._ragged_prompt(prompt, B, prompt_lens)
+        if p_lens is not None and self.spk_encoder is not None:
+            raise NotImplementedError("prompt_lens with a speaker encoder: it reads the padded prompt with no mask")
         x, lens = self._ragged_text(x, B, x_lens)
         x = (x.unsqueeze(0).expand(B, -1) if x.dim() == 1 else x).to(device)   # 1-D: one text for every row
         enc_mask = cross_mask = None
@@ -190,13 +201,31 @@ class LinaModel(nn.Module):
         y_embd = self.rvq_embed.embed_sum(torch.ones(Q, B, 1, dtype=torch.long, device=device))
 
         p_len = -1
+        prompt_tok = None
         if prompt is not None:
             if prompt.shape[1] != B:
                 prompt = prompt.expand(Q, B, -1) + 3
-            prompt = self.rvq_embed.embed_sum(prompt.to(device))
+            prompt_tok = prompt.to(device)
+            prompt = self.rvq_embed.embed_sum(prompt_tok)
             p_len = prompt.shape[1]
             if self.spk_encoder is not None:
                 prompt[:, 0] = self.spk_encoder(prompt)
+
+        # prompts of different lengths: positions 0 .. min(p) are common to every row (the prefill below, as for one p_len);
+        # from there row b is fed prompt[b, t] while t < p_b -- `fed(t, picks)` is the reference's line 175 per row
+        p_dev = None
+        if p_lens is not None:
+            p_dev = p_lens.to(device)
+            p_len = int(p_lens.min())
+
+        def fed(t, q_sampled):
+            if prompt is None or (p_dev is None and t >= p_len):
+                return self.rvq_embed.embed_sum(q_sampled)
+            if p_dev is None:
+                return prompt[:, [t]]
+            if t >= prompt.shape[1]:
+                return self.rvq_embed.embed_sum(q_sampled)
+            return torch.where((t < p_dev)[:, None, None], prompt[:, [t]], self.rvq_embed.embed_sum(q_sampled))
 
         mode = engine or "auto"
         if mode not in ("auto", "loop", "fused", "module"):
@@ -261,12 +290,13 @@ class LinaModel(nn.Module):
             if n_pre > 0:
                 pre_q = torch.cat([pick_tokens(pre_logits[:, t:t + 1]) for t in range(n_pre)], dim=2)   # [Q,B,n_pre]
                 preload = (pre_q, pre_att)
-                y0 = prompt[:, [n_pre - 1]] if n_pre - 1 < p_len else self.rvq_embed.embed_sum(pre_q[:, :, -1:])
+                y0 = fed(n_pre - 1, pre_q[:, :, -1:])          # (one p_len: the prompt token if n_pre - 1 < p_len, else the pick's)
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)))
             qs, atts, n = eng.generate(max_seqlen, y0, k=k, temp=temp, first_greedy_quant=first_greedy_quant, seed=seed,
                                        force_max_seqlen=force_max_seqlen, stop_check_every=stop_check_every,
-                                       log_att=True, preload=preload)
+                                       log_att=True, preload=preload,
+                                       forced=None if p_lens is None else (prompt_tok, p_lens))
             return self._finish_generate(qs, atts, (qs == 2).all(dim=0), B, device, lens)
 
         all_stop = torch.zeros(B, 1, dtype=torch.bool, device=device)
@@ -288,7 +318,7 @@ class LinaModel(nn.Module):
                 if bool(flags.any()):
                     stop_at = int(torch.nonzero(flags)[0])
                     break
-            y_embd = prompt[:, [t]] if (prompt is not None and t < p_len) else self.rvq_embed.embed_sum(q_sampled)
+            y_embd = fed(t, q_sampled)
 
         if stop_at is not None:             # trim to what a per-step check would have produced
             qs, atts, stop_tokens = qs[:stop_at + 1], atts[:stop_at + 1], stop_tokens[:stop_at + 1]
@@ -320,6 +350,35 @@ class LinaModel(nn.Module):
             raise ValueError(f"x has {x.shape[0]} rows for batch_size {B}")
         lens = torch.tensor(text_lengths(x_lens, B, x.shape[1]), dtype=torch.long)
         return x, (None if bool((lens == x.shape[1]).all()) else lens)
+
+    @staticmethod
+    def _ragged_prompt(prompt, B: int, prompt_lens):
+        """generate_batch's prompt argument -> (prompt, lengths [B] LongTensor or None).  A list of B prompts [Q, p_i] is
+        right-padded with 0 and its lengths derived; lengths that are all the padded width mean one p_len (None: today's
+        path)."""
+        from .decode import prompt_lengths
+        if isinstance(prompt, (list, tuple)):
+            if prompt_lens is not None:
+                raise ValueError("prompt_lens: the list form of prompt carries its own lengths")
+            if len(prompt) != B:
+                raise ValueError(f"prompt is a list of {len(prompt)} excerpts: batch_size must equal it (got {B})")
+            if any(p.dim() != 2 or p.shape[0] != prompt[0].shape[0] for p in prompt):
+                raise ValueError("prompt as a list: one LongTensor [Q, p_i] per row")
+            prompt_lens = [int(p.shape[1]) for p in prompt]
+            P = max(prompt_lens)
+            padded = torch.zeros(prompt[0].shape[0], B, P, dtype=torch.long, device=prompt[0].device)
+            for i, p in enumerate(prompt):
+                padded[:, i, :p.shape[1]] = p
+            prompt = padded
+        if prompt_lens is None:
+            return prompt, None
+        if prompt is None:
+            raise ValueError("prompt_lens needs a prompt")
+        if prompt.dim() != 3 or prompt.shape[1] != B:
+            raise ValueError(f"prompt_lens needs prompt as [Q, B, P] right-padded excerpts, one per row (B = {B}): the "
+                             "broadcast (+3) rule belongs to the one-prompt form")
+        lens = torch.tensor(prompt_lengths(prompt_lens, B, prompt.shape[2]), dtype=torch.long)
+        return prompt, (None if bool((lens == prompt.shape[2]).all()) else lens)
 
     def _finish_generate(self, qs, atts, is_stop, B, device, lens=None):
         """Post-processing of the reference (modeling_lina.py:180-192) from the [B,n] stop flags: the stop-flag matrix
