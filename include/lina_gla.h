@@ -493,6 +493,11 @@ int lina_gla_decode_window_persist(const void* q, const void* k, const void* v, 
                                    int64_t gate_sb, int64_t gate_sh, float eps, int og_packed,
                                    int dtype, int g_dtype, float scale, int n_wg, lina_stream_t stream);
 
+/* TEST ONLY: the four-at-a-time 64-lane sum of the K1w kernels (wave_sum4) on its own.  x: fp32 [n_waves][4][64],
+ * out: fp32 [n_waves][4] -- out[w][i] = the sum of x[w][i][0 .. 63] in the order of an xor butterfly (pairs, quads, ...,
+ * halves), so that the device code path can be compared bit for bit with a reference that shares no code with it. */
+int lina_wave_sum_selftest(const float* x, float* out, int n_waves, lina_stream_t stream);
+
 /* Decode-step projection with fused neighbours: out[M,N] = epi(A[M,K] . W[N,K]^T), M ~ batch rows.
  *   ln_dim > 0 : A is layer-normalised over its ln_dim features first, folded algebraically:
  *                out = rstd*(A.W^T - mu*c1) + c2   with W pre-scaled by the LN gamma,

@@ -39,10 +39,65 @@
 #else
 #define LINA_K1W_STATE_LOAD(p) ld_nt4(p)
 #endif
+#ifndef LINA_K1W_SUMS_BUTTERFLY
+#define LINA_K1W_SUMS_BUTTERFLY 0  // the 64-lane sums as one shfl_xor butterfly each, under `s <= j` branches (the form before wave_sum4)
+#endif
 
 namespace lina {
 
 constexpr int kWinMax = 16;
+
+// Four 64-lane sums at once; every lane gets all four.  The 16 lanes of a DPP row are summed by row_scan4 (lane 16 r + 15
+// then holds row r: pairs, quads, eights, sixteen -- the tree of an xor butterfly over masks 1, 2, 4, 8), the four row sums
+// are fetched and added as (r0 + r1) + (r2 + r3) -- the butterfly's masks 16 and 32.  fp32 addition is commutative, so
+// each result equals  a += shfl_xor(a, 1); ... a += shfl_xor(a, 32)  bit for bit, at ONE cross-lane latency for the four
+// values (16 independent fetches behind 16 VALU adds) where a butterfly has six dependent ones per value.
+__device__ __forceinline__ void wave_sum4(float& a, float& b, float& c, float& d) {
+    row_scan4(a, b, c, d);
+    const float a0 = shfl(a, 15), a1 = shfl(a, 31), a2 = shfl(a, 47), a3 = shfl(a, 63);
+    const float b0 = shfl(b, 15), b1 = shfl(b, 31), b2 = shfl(b, 47), b3 = shfl(b, 63);
+    const float c0 = shfl(c, 15), c1 = shfl(c, 31), c2 = shfl(c, 47), c3 = shfl(c, 63);
+    const float d0 = shfl(d, 15), d1 = shfl(d, 31), d2 = shfl(d, 47), d3 = shfl(d, 63);
+    a = (a0 + a1) + (a2 + a3);
+    b = (b0 + b1) + (b2 + b3);
+    c = (c0 + c1) + (c2 + c3);
+    d = (d0 + d1) + (d2 + d3);
+}
+// one 64-lane sum (the K5 tail's sum of squares): the same tree
+__device__ __forceinline__ float wave_sum1(float a) {
+#if LINA_K1W_SUMS_BUTTERFLY
+    a += shfl_xor(a, 1); a += shfl_xor(a, 2); a += shfl_xor(a, 4);
+    a += shfl_xor(a, 8); a += shfl_xor(a, 16); a += shfl_xor(a, 32);
+#else
+    float z0 = 0.f, z1 = 0.f, z2 = 0.f;
+    wave_sum4(a, z0, z1, z2);
+#endif
+    return a;
+}
+
+// The pending window terms of the K5 tail, N steps at a time:  r += sum_s a_s v_s  over s0 <= s < s0 + N, s <= j  (j is
+// workgroup-uniform), a_s = the sum of the row blocks' partial sums a[s][0 .. NRB-1], v_s = four columns of the window's v
+// row s.  All the LDS reads of the N steps are issued before the first use (slots past j hold values nobody uses): one LDS
+// latency per N steps; the additions and FMAs keep the order s = s0, s0 + 1, ...
+template <int N, int NRB>
+__device__ __forceinline__ void pending_terms(float4& r, const float (*a)[NRB], const float* v4, int v_stride, int s0, int j) {
+    float as[N];
+    float4 vs[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        float t = a[s0 + u][0];
+#pragma unroll
+        for (int g2 = 1; g2 < NRB; ++g2) t += a[s0 + u][g2];
+        as[u] = t;
+        vs[u] = *reinterpret_cast<const float4*>(v4 + (s0 + u) * v_stride);
+    }
+#pragma unroll
+    for (int u = 0; u < N; ++u)
+        if (s0 + u <= j) {
+            r.x = fmaf(as[u], vs[u].x, r.x); r.y = fmaf(as[u], vs[u].y, r.y);
+            r.z = fmaf(as[u], vs[u].z, r.z); r.w = fmaf(as[u], vs[u].w, r.w);
+        }
+}
 
 __device__ __forceinline__ float ld_hist(const float* p) {
 #if LINA_K1W_HIST_NT
@@ -173,6 +228,7 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_kernel(
         }
         s_q[row] = qj;
         s_e[row] = __expf(cj);
+#if LINA_K1W_SUMS_BUTTERFLY
 #pragma unroll
         for (int s = 0; s < kWinMax; ++s) {
             if (s <= j) {                                                // workgroup-uniform
@@ -184,6 +240,29 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_kernel(
                 if (t256 == 0) s_a[s][rb] = a;
             }
         }
+#else
+        // four slots at a time, only the groups that hold a slot <= j (workgroup-uniform): inside a group no branch -- its
+        // slots past j (history registers 0) give values that nobody reads -- and the group's four sums
+        // <q (.) e^{c_j - c_s}, k_s> over this row block share one cross-lane latency (wave_sum4); no sums at the
+        // write-back position, which applies w_s to the state and never reads s_a
+#pragma unroll
+        for (int s0 = 0; s0 < kWinMax; s0 += 4) {
+            if (s0 <= j) {
+                float a[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int s = s0 + u;
+                    const float ws = (!flush_only && s == j) ? kj : __expf(cj - h1[s]) * h2[s];
+                    s_w[s][row] = ws;
+                    a[u] = qj * ws;
+                }
+                if (!write_back) {
+                    wave_sum4(a[0], a[1], a[2], a[3]);
+                    if (t256 == 0) { s_a[s0][rb] = a[0]; s_a[s0 + 1][rb] = a[1]; s_a[s0 + 2][rb] = a[2]; s_a[s0 + 3][rb] = a[3]; }
+                }
+            }
+        }
+#endif
     } else {
         if (vc < DV) {
 #pragma unroll
@@ -257,41 +336,36 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_kernel(
         // ---- wave 0 finishes the head: sum of the NRB*RPI row-group partials (+ the pending window terms), then K5:
         // RMS-normalise over Dv, weight, swish gate (reference model/gla.py:219)
         constexpr int CG4 = DV / 4;                               // the tail's lanes: four columns each, whatever EPL
+        const int tl = lane_id();                                 // = tid, from the hardware: as one value of the whole
+        const int c4 = 4 * tl;                                    // kernel 4 * tid is kept (spilled) beside the tile
         float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tid < CG4) {
-            r = *reinterpret_cast<const float4*>(&s_red[4 * tid]);
+        if (tl < CG4) {
+            r = *reinterpret_cast<const float4*>(&s_red[c4]);
 #pragma unroll
             for (int jj = 1; jj < NRB * RPI; ++jj) {
-                const float4 t = *reinterpret_cast<const float4*>(&s_red[jj * DV + 4 * tid]);
+                const float4 t = *reinterpret_cast<const float4*>(&s_red[jj * DV + c4]);
                 r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w;
             }
-            if (!write_back)            // pending window terms: sum_s <q (.) e^{c_j - c_s}, k_s> v_s
-                for (int s = 0; s <= j; ++s) {
-                    float a = s_a[s][0];
-#pragma unroll
-                    for (int g2 = 1; g2 < NRB; ++g2) a += s_a[s][g2];
-                    const float4 vv = *reinterpret_cast<const float4*>(&s_v[s][4 * tid]);
-                    r.x = fmaf(a, vv.x, r.x); r.y = fmaf(a, vv.y, r.y); r.z = fmaf(a, vv.z, r.z); r.w = fmaf(a, vv.w, r.w);
-                }
+            if (!write_back) {          // pending window terms: sum_s <q (.) e^{c_j - c_s}, k_s> v_s
+                for (int s0 = 0; s0 <= j; s0 += 4) pending_terms<4, NRB>(r, s_a, &s_v[0][c4], DV, s0, j);
+            }
         }
-        float ss = r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w;
-        ss += shfl_xor(ss, 1); ss += shfl_xor(ss, 2); ss += shfl_xor(ss, 4);
-        ss += shfl_xor(ss, 8); ss += shfl_xor(ss, 16); ss += shfl_xor(ss, 32);
+        const float ss = wave_sum1(r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w);
         // finish columns [c0, c0 + DV) of the head from the un-normalised values r (lane = 4 columns)
         auto finish = [&](float4 x, int c0, float rs) {
-            if (tid < CG4) {
+            if (tl < CG4) {
                 x.x *= rs; x.y *= rs; x.z *= rs; x.w *= rs;
 #if LINA_K1W_NO_TAIL_LOADS
                 const float4 ww = make_float4(1.f, 1.f, 1.f, 1.f), gg = make_float4(eps, scale, eps, scale);
 #else
-                const float4 ww = ld4(nw + c0 + 4 * tid);
-                const float4 gg = ld4(gate + b * gate_sb + h * gate_sh + c0 + 4 * tid);
+                const float4 ww = ld4(nw + c0 + 4 * tl);
+                const float4 gg = ld4(gate + b * gate_sb + h * gate_sh + c0 + 4 * tl);
 #endif
                 x.x *= ww.x; x.y *= ww.y; x.z *= ww.z; x.w *= ww.w;
                 x.x *= gg.x * sigmoidf(gg.x); x.y *= gg.y * sigmoidf(gg.y);
                 x.z *= gg.z * sigmoidf(gg.z); x.w *= gg.w * sigmoidf(gg.w);
-                if (og_packed) st4(og + packed_off<TIO>(b, h * DVT + c0 + 4 * tid, H * DVT), x);   // 4 | KL: one piece
-                else st4(og + (int64_t)bh * DVT + c0 + 4 * tid, x);
+                if (og_packed) st4(og + packed_off<TIO>(b, h * DVT + c0 + 4 * tl, H * DVT), x);   // 4 | KL: one piece
+                else st4(og + (int64_t)bh * DVT + c0 + 4 * tl, x);
             }
         };
         if constexpr (CS == 1) {
@@ -299,13 +373,13 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_kernel(
         } else {
             // publish this half, take a ticket; the LAST arriver reads the other halves and normalises the whole head
             float* ox = o_x + (int64_t)bh * DVT;
-            if (tid < CG4) { st_agent8(ox + col0 + 4 * tid, r.x, r.y); st_agent8(ox + col0 + 4 * tid + 2, r.z, r.w); }
+            if (tl < CG4) { st_agent8(ox + col0 + 4 * tl, r.x, r.y); st_agent8(ox + col0 + 4 * tl + 2, r.z, r.w); }
             drain_stores();
             int t = 0;
-            if (tid == 0) t = ticket_agent(&counters[bh]);
+            if (tl == 0) t = ticket_agent(&counters[bh]);
             t = shfl_i(t, 0);
             if (t == CS - 1) {
-                if (tid == 0) counters[bh] = 0;                     // re-armed for the next launch
+                if (tl == 0) counters[bh] = 0;                     // re-armed for the next launch
                 float4 oth[CS];
                 float tot = ss;
 #pragma unroll
@@ -313,8 +387,8 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_kernel(
                     oth[c] = r;
                     if (c != (int)blockIdx.y) {
                         float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (tid < CG4) {
-                            const float2 lo = ld_agent8(ox + c * DV + 4 * tid), hi = ld_agent8(ox + c * DV + 4 * tid + 2);
+                        if (tl < CG4) {
+                            const float2 lo = ld_agent8(ox + c * DV + 4 * tl), hi = ld_agent8(ox + c * DV + 4 * tl + 2);
                             x = make_float4(lo.x, lo.y, hi.x, hi.y);
                         }
                         float s2 = x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
@@ -342,7 +416,7 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_kernel(
 // write-back's stores interleave with the next head's loads instead of following a chip-wide read phase.  The next head's
 // small loads (history, q / k / v / g, gate) are issued BEFORE its tile (a wave's loads return in order) and kept RAW until
 // the bookkeeping that follows the current head's pieces; the LDS arrays are double-buffered (head parity), one barrier
-// pair per head as above: wave 0's K5 tail of head n runs beside the other waves' bookkeeping of head n + 1.  No workgroup
+// pair per head as above: the K5 tail of head n (the last wave's) runs beside the row waves' bookkeeping of head n + 1.  No workgroup
 // waits for another one.
 //
 // The compiler counts the waits (vmcnt) itself, and where paths with different numbers of loads meet it assumes the
@@ -392,7 +466,7 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
         __attribute__((aligned(16))) float red[NRB * RPI * DV];
         float w[kWinPersist][DK];
         float q[DK], e[DK], a[kWinPersist][NRB];
-        typename raw4<TIO>::type gate[CG4];                     // the head's gate row for wave 0's tail, raw
+        typename raw4<TIO>::type gate[CG4];                     // the head's gate row for the tail wave, raw
     };
     __shared__ head_lds s_buf[2];
     __shared__ typename raw4<TIO>::type s_nw[CG4];              // the norm weight: the same for every head
@@ -412,6 +486,10 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
     const int s_last = n_hist > 0 ? n_hist - 1 : 0;
     constexpr int NV = 192 * NRB;
     const bool row_wave = wave_uniform(t256 < RB ? 1 : 0) != 0;        // the first wave of each thread group, as a scalar
+    // the K5 tail of a head belongs to the LAST wave: never a row wave, and at Dk >= 128 without v columns -- it has no
+    // bookkeeping of the next head to do behind the tail (wave 0 has a row block's)
+    const bool tail_wave = wave_uniform(tid >= 256 * NRB - 64 ? 1 : 0) != 0;
+    const int tl = tid & 63;                                           // the tail's lane: four columns each
     const int row = r0 + (t256 & (RB - 1));
     const int vc = rb * 192 + t256 - RB;                               // v column of a non-row thread (first pass)
     const int vcc = vc < 0 ? 0 : (vc < DV ? vc : DV - 1);              // ... clamped: every lane loads
@@ -435,7 +513,7 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
     decltype(ld_raw(gk)) gj_r;
     decltype(ld_raw(q)) kj_r, qj_r, vj_r;
     typename raw4<TIO>::type gate_r;
-    if (tid < CG4) s_nw[tid] = ld4_raw(nw + 4 * tid);                  // read by wave 0 behind the first head's barriers
+    if (tid < CG4) s_nw[tid] = ld4_raw(nw + 4 * tid);                  // read by the tail wave behind the first head's barriers
     auto small_loads = [&](int hd) __attribute__((always_inline)) {
         const int b = hd / H, h = hd % H;
 #pragma unroll
@@ -466,7 +544,7 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
         const int64_t hoff = (int64_t)bh * DK;
         head_lds& L = s_buf[p];
         // ---- per-row gate bookkeeping and the window's v rows of head bh -> LDS buffer p
-        if (tid < CG4) L.gate[tid] = gate_r;
+        if (tail_wave && tl < CG4) L.gate[tl] = gate_r;
         if (row_wave) {
             const float gj = cvt1(gj_r), kj = cvt1(kj_r), qj = cvt1(qj_r) * scale;
             float cprev = 0.0f;
@@ -477,6 +555,7 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
             st_hist(at_byte(hist_k + ((int64_t)j * BH * DK + hoff), row * 4), kj);
             L.q[row] = qj;
             L.e[row] = __expf(cj);
+#if LINA_K1W_SUMS_BUTTERFLY
 #pragma unroll
             for (int s = 0; s < kWinPersist; ++s) {
                 if (s <= j) {                                            // workgroup-uniform
@@ -488,6 +567,27 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
                     if (t256 == 0) L.a[s][rb] = a;
                 }
             }
+#else
+            // This sits between the last piece of the previous head and the barrier that opens this one, with most waves
+            // idle: no branch around a slot (the clamped history of the slots past j gives values that nobody reads), the
+            // sums <q (.) e^{c_j - c_s}, k_s> over this row block four at a time (wave_sum4: two cross-lane latencies for
+            // the window where one butterfly per slot had 6 (j + 1)), and none at the write-back position, which applies
+            // w_s to the state and never reads L.a
+            float ws[kWinPersist];
+#pragma unroll
+            for (int s = 0; s < kWinPersist; ++s) {
+                ws[s] = (s == j) ? kj : __expf(cj - h1[s < NH ? s : 0]) * h2[s < NH ? s : 0];
+                L.w[s][row] = ws[s];
+            }
+            if (!WB) {
+#pragma unroll
+                for (int s0 = 0; s0 < kWinPersist; s0 += 4) {
+                    float a0 = qj * ws[s0], a1 = qj * ws[s0 + 1], a2 = qj * ws[s0 + 2], a3 = qj * ws[s0 + 3];
+                    wave_sum4(a0, a1, a2, a3);
+                    if (t256 == 0) { L.a[s0][rb] = a0; L.a[s0 + 1][rb] = a1; L.a[s0 + 2][rb] = a2; L.a[s0 + 3][rb] = a3; }
+                }
+            }
+#endif
         } else {
             if (vc < DV) {
                 const float vj = cvt1(vj_r);
@@ -576,38 +676,32 @@ __global__ __launch_bounds__(256 * NRB) void gla_decode_window_persist_kernel(
         for (int e4 = 0; e4 < EPL; e4 += 4)
             *reinterpret_cast<float4*>(&L.red[(rb * RPI + rg) * DV + EPL * cg + e4]) = make_float4(acc[e4], acc[e4 + 1], acc[e4 + 2], acc[e4 + 3]);
         __syncthreads();
-        if (tid < 64) {
-            // ---- wave 0 finishes head bh (the sum, the pending window terms, K5) while the other waves go on
+        if (tail_wave) {
+            // ---- the last wave finishes head bh (the sum, the pending window terms, K5) while the other waves go on
             float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (tid < CG4) {
-                r = *reinterpret_cast<const float4*>(&L.red[4 * tid]);
+            if (tl < CG4) {
+                r = *reinterpret_cast<const float4*>(&L.red[4 * tl]);
 #pragma unroll
                 for (int jj = 1; jj < NRB * RPI; ++jj) {
-                    const float4 t = *reinterpret_cast<const float4*>(&L.red[jj * DV + 4 * tid]);
+                    const float4 t = *reinterpret_cast<const float4*>(&L.red[jj * DV + 4 * tl]);
                     r.x += t.x; r.y += t.y; r.z += t.z; r.w += t.w;
                 }
-                if (!WB)                // pending window terms: sum_s <q (.) e^{c_j - c_s}, k_s> v_s
-                    for (int s = 0; s <= j; ++s) {
-                        float a = L.a[s][0];
-#pragma unroll
-                        for (int g2 = 1; g2 < NRB; ++g2) a += L.a[s][g2];
-                        const float4 vv = *reinterpret_cast<const float4*>(&L.v[s][4 * tid]);
-                        r.x = fmaf(a, vv.x, r.x); r.y = fmaf(a, vv.y, r.y); r.z = fmaf(a, vv.z, r.z); r.w = fmaf(a, vv.w, r.w);
-                    }
+                if (!WB) {              // pending window terms: sum_s <q (.) e^{c_j - c_s}, k_s> v_s
+                    pending_terms<4, NRB>(r, L.a, &L.v[0][4 * tl], DV, 0, j);
+                    if (j >= 4) pending_terms<4, NRB>(r, L.a, &L.v[0][4 * tl], DV, 4, j);
+                }
             }
-            float ss = r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w;
-            ss += shfl_xor(ss, 1); ss += shfl_xor(ss, 2); ss += shfl_xor(ss, 4);
-            ss += shfl_xor(ss, 8); ss += shfl_xor(ss, 16); ss += shfl_xor(ss, 32);
-            if (tid < CG4) {
+            const float ss = wave_sum1(r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w);
+            if (tl < CG4) {
                 const float rs = rsqrtf(ss / (float)DV + eps);
                 float4 x = r;
                 x.x *= rs; x.y *= rs; x.z *= rs; x.w *= rs;
-                const float4 ww = cvt4(s_nw[tid]), gg = cvt4(L.gate[tid]);
+                const float4 ww = cvt4(s_nw[tl]), gg = cvt4(L.gate[tl]);
                 x.x *= ww.x; x.y *= ww.y; x.z *= ww.z; x.w *= ww.w;
                 x.x *= gg.x * sigmoidf(gg.x); x.y *= gg.y * sigmoidf(gg.y);
                 x.z *= gg.z * sigmoidf(gg.z); x.w *= gg.w * sigmoidf(gg.w);
-                if (og_packed) st4(og + packed_off<TIO>(b, h * DV + 4 * tid, H * DV), x);
-                else st4(og + (int64_t)bh * DV + 4 * tid, x);
+                if (og_packed) st4(og + packed_off<TIO>(b, h * DV + 4 * tl, H * DV), x);
+                else st4(og + (int64_t)bh * DV + 4 * tl, x);
             }
         }
     };
@@ -688,7 +782,23 @@ static int launch_window_persist(const void* q, const void* k, const void* v, co
     return check_launch("lina_gla_decode_window_persist");
 }
 
+// test only: wave w sums x[w][0 .. 3][0 .. 63] with wave_sum4 -> out[w][0 .. 3]
+__global__ __launch_bounds__(64) void wave_sum_selftest_kernel(const float* __restrict__ x, float* __restrict__ out) {
+    const int w = blockIdx.x, l = threadIdx.x;
+    float a = x[(w * 4 + 0) * 64 + l], b = x[(w * 4 + 1) * 64 + l], c = x[(w * 4 + 2) * 64 + l], d = x[(w * 4 + 3) * 64 + l];
+    wave_sum4(a, b, c, d);
+    if (l == 0) { out[w * 4 + 0] = a; out[w * 4 + 1] = b; out[w * 4 + 2] = c; out[w * 4 + 3] = d; }
+}
+
 }  // namespace lina
+
+extern "C" int lina_wave_sum_selftest(const float* x, float* out, int n_waves, lina_stream_t stream) {
+    using namespace lina;
+    LINA_REQUIRE(x && out, "lina_wave_sum_selftest: null pointer");
+    LINA_REQUIRE(n_waves > 0, "lina_wave_sum_selftest: n_waves must be positive");
+    LINA_LAUNCH(wave_sum_selftest_kernel, dim3((unsigned)n_waves), dim3(64), 0, stream, x, out);
+    return check_launch("lina_wave_sum_selftest");
+}
 
 extern "C" int lina_gla_decode_window_max(void) { return lina::kWinMax; }
 

@@ -664,6 +664,18 @@ def gla_decode_window_flush(state, hist_k, hist_c, hist_v, n_pending: int):
     return state
 
 
+def wave_sum_selftest(x):
+    """TEST ONLY (lina_wave_sum_selftest): x fp32 [n_waves, 4, 64] -> [n_waves, 4], each the 64-lane sum the K1w kernels form
+    with wave_sum4 (the addition order of an xor butterfly)."""
+    be = _backend._BACKEND
+    be.require(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 3 or tuple(x.shape[1:]) != (4, 64):
+        raise ValueError("x must be contiguous fp32 [n_waves, 4, 64]")
+    out = torch.empty(x.shape[0], 4, dtype=torch.float32, device=x.device)
+    _check(be.lib.lina_wave_sum_selftest(_ptr(x), _ptr(out), int(x.shape[0]), be.stream(x)))
+    return out
+
+
 def cross_att_step1(q_lin, ln_w, ln_b, ln_eps, kk, pe, att1, xp, scale):
     """Blind cross-attention step 1 (see lina_gla.h).  att1: [B,T_txt] view (row stride free), written in place."""
     be = _backend._BACKEND
