@@ -239,6 +239,23 @@ int lina_pick_embed_forced(const void* logits, int64_t row_stride, const void* t
                            int L, int n_emb, int d, int max_steps, int n_sampled, int k, float temp, uint64_t seed,
                            const int64_t* force_tok, const int* force_len, int P_cap, int dtype, lina_stream_t stream);
 
+/* K6g -- re-arm batch rows for a new utterance between two replays of the decode loop (LinaModel.generate_queue: a row
+ * whose utterance has ended takes the next queued text while the other rows go on).  For each of the n listed rows
+ * b = rows[i] (int32 on the device, distinct, each in [0, B), 1 <= n <= B):
+ *   - row b of every state segment is zeroed with 16-byte stores.  Segment s is one state tensor (a conv cache or a recurrent
+ *     state, fp32 or bf16) whose row b starts at seg_ptr[s] + b * seg_row_bytes[s]; seg_ptr (uint64 [n_seg]) and
+ *     seg_row_bytes (int64 [n_seg]) live on the device, seg_row_bytes_host is the host copy of the latter -- it sizes the grid
+ *     and is checked here: every entry a positive multiple of 16, else LINA_ERR_ARG, as for a null table.  Every row start
+ *     must be 16-byte aligned;
+ *   - x_out[b,:] = y_start ([d], the start-token embedding) and, with x_out_packed, its fragment-major copy (the store of
+ *     K6d / K6e / K6f: bit-equal to packing the row-major result);
+ *   - txt_len[b] = new_len[i] (both int32, optional: txt_len needs new_len).
+ * loop_ctl (optional): ONE workgroup clears the stop flags [LINA_LOOP_CTL_ROWS + b] of the listed rows, subtracts the number
+ * that were set from word [0] and sets word [1] = -1.  Rows that are not listed are not touched. */
+int lina_rows_rearm(const int* rows, int n, int B, const uint64_t* seg_ptr, const int64_t* seg_row_bytes,
+                    const int64_t* seg_row_bytes_host, int n_seg, const void* y_start, void* x_out, void* x_out_packed,
+                    int d, int* loop_ctl, int* txt_len, const int* new_len, int dtype, lina_stream_t stream);
+
 /* K6b -- greedy pick: out[r] = argmax_j logits[r,j], lowest index on exact ties.
  * Replaces topk_sampling(k=1) (reference model/tools.py:38-44, modeling_lina.py:159-164);
  * identical except on exact ties, where the reference draws uniformly among them. */

@@ -64,6 +64,18 @@ __device__ __forceinline__ void note_stop(int* ctl, const int* toks, int Q, int 
     if (ticket_agent(ctl + kCtlCount) == B - 1) ctl[kCtlStopAt] = (int)t;   // this row was the last one still running
 }
 
+// Four elements e .. e+3 of row b of the step's input: row-major and -- with x_pk -- fragment-major (the store K6d / K6e /
+// K6f / K6g share).
+template <typename T>
+__device__ __forceinline__ void put_row4(T* __restrict__ x_out, T* __restrict__ x_pk, int b, int e, int d, float4 acc) {
+    st4(x_out + (int64_t)b * d + e, acc);
+    if (x_pk) {                                  // fragment-major copy (the model-dtype values just stored)
+        T tmp4[4];
+        st4(tmp4, acc);
+        st4(x_pk + packed_off<T>(b, e, d), ld4(tmp4));
+    }
+}
+
 // The next step's input of row b, x_out[b,:] = sum_q table[q, toks[q], :] (K6a's order and precision: bit-equal to
 // lina_embed_sum on the same tokens), row-major and -- with x_pk -- fragment-major.  toks: Q non-negative ids in LDS.
 template <typename T>
@@ -77,12 +89,7 @@ __device__ __forceinline__ void embed_row(const int* toks, const T* __restrict__
             const float4 r = ld4(table + ((int64_t)qi * n_emb + tok) * d + e);
             acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
         }
-        st4(x_out + (int64_t)b * d + e, acc);
-        if (x_pk) {                                  // fragment-major copy (the model-dtype values just stored)
-            T tmp4[4];
-            st4(tmp4, acc);
-            st4(x_pk + packed_off<T>(b, e, d), ld4(tmp4));
-        }
+        put_row4(x_out, x_pk, b, e, d, acc);
     }
 }
 
@@ -213,7 +220,98 @@ __global__ __launch_bounds__(256) void sample_pick_embed_kernel(const T* __restr
     }
 }
 
+
+// K6g -- re-arm a list of batch rows for a new utterance BETWEEN two replays of the decode loop's graphs (a row that has
+// stopped takes the next queued text while its neighbours go on decoding): for every listed row b = rows[i]
+//   * row b of every state segment (conv caches and recurrent state of every block; segment s is one tensor whose row b
+//     starts at seg_ptr[s] + b * seg_row_bytes[s]) is zeroed with 16-byte stores,
+//   * x_out[b,:] (and its fragment-major copy) = y_start, the start-token embedding,
+//   * txt_len[b] = new_len[i],
+// and ONE workgroup clears the listed rows' stop flags in the loop-control block, takes their number off word [0] and sets
+// word [1] = -1.  Grid (G, n): the 16-byte units of row i's segments, taken as one concatenated range, are dealt out
+// round-robin to the G x 256 threads of grid row i.  Rows that are not listed are not touched.
+template <typename T>
+__global__ __launch_bounds__(256) void rows_rearm_kernel(const int* __restrict__ rows, int n, int B,
+                                                         const uint64_t* __restrict__ seg_ptr,
+                                                         const int64_t* __restrict__ seg_row_bytes, int n_seg,
+                                                         const T* __restrict__ y_start, T* __restrict__ x_out,
+                                                         T* __restrict__ x_pk, int d, int* ctl, int* txt_len,
+                                                         const int* __restrict__ new_len) {
+    __shared__ int s_cnt;
+    const int i = blockIdx.y, tid = threadIdx.x;
+    const int b = rows[i];
+    const bool valid = b >= 0 && b < B;              // (the caller's contract; a bad id writes nothing)
+    if (valid) {
+        const int64_t stride = (int64_t)gridDim.x * 256, g0 = (int64_t)blockIdx.x * 256 + tid;
+        int64_t base = 0;                            // 16-byte units of the segments before s
+        for (int s = 0; s < n_seg; ++s) {
+            const int64_t rb = seg_row_bytes[s], units = rb >> 4;
+            const uint64_t p0 = seg_ptr[s];
+            int64_t u = (g0 - base) % stride;
+            if (u < 0) u += stride;
+            if (p0 != 0 && rb > 0) {
+                uint4* row = reinterpret_cast<uint4*>(p0 + (uint64_t)b * (uint64_t)rb);
+                for (; u < units; u += stride) row[u] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            base += units;
+        }
+        if (blockIdx.x == 0) {
+            for (int e = tid * 4; e < d; e += 256 * 4) put_row4(x_out, x_pk, b, e, d, ld4(y_start + e));
+            if (txt_len && tid == 0) txt_len[b] = new_len[i];
+        }
+    }
+    if (ctl && blockIdx.x == 0 && blockIdx.y == 0) {           // rows are distinct: no two threads meet on a flag
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        for (int r = tid; r < n; r += 256) {
+            const int br = rows[r];
+            if (br >= 0 && br < B && ctl[kCtlRows + br]) {
+                ctl[kCtlRows + br] = 0;
+                lds_atomic_add(&s_cnt, 1);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            ctl[kCtlCount] -= s_cnt;
+            ctl[kCtlStopAt] = -1;
+        }
+    }
+}
+
 }  // namespace lina
+
+extern "C" int lina_rows_rearm(const int* rows, int n, int B, const uint64_t* seg_ptr, const int64_t* seg_row_bytes,
+                               const int64_t* seg_row_bytes_host, int n_seg, const void* y_start, void* x_out,
+                               void* x_out_packed, int d, int* loop_ctl, int* txt_len, const int* new_len, int dtype,
+                               lina_stream_t stream) {
+    using namespace lina;
+    LINA_REQUIRE(rows && y_start && x_out, "lina_rows_rearm: null pointer");
+    LINA_REQUIRE(seg_ptr && seg_row_bytes && seg_row_bytes_host, "lina_rows_rearm: null segment table");
+    LINA_REQUIRE(B > 0 && n >= 1 && n <= B, "lina_rows_rearm: n=%d must be in [1, B=%d]", n, B);
+    LINA_REQUIRE(n_seg >= 1, "lina_rows_rearm: n_seg=%d must be positive", n_seg);
+    LINA_REQUIRE(d > 0 && d % 4 == 0, "lina_rows_rearm: d=%d must be a positive multiple of 4", d);
+    LINA_REQUIRE(valid_dtype(dtype), "lina_rows_rearm: bad dtype %d", dtype);
+    LINA_REQUIRE(!x_out_packed || d % (dtype == LINA_BF16 ? 32 : 16) == 0, "lina_rows_rearm: packed copy needs whole k-steps");
+    LINA_REQUIRE(!txt_len || new_len, "lina_rows_rearm: txt_len needs new_len");
+    int64_t units = 0;
+    for (int s = 0; s < n_seg; ++s) {
+        const int64_t rb = seg_row_bytes_host[s];
+        LINA_REQUIRE(rb > 0 && rb % 16 == 0, "lina_rows_rearm: row_bytes[%d]=%lld must be a positive multiple of 16", s,
+                     (long long)rb);
+        units += rb / 16;
+    }
+    // 8 stores per thread, at most 2048 workgroups per row (a row of the L169 stack: 13.6 MB = 850 k units -> 416 workgroups)
+    int64_t G = (units + 256 * 8 - 1) / (256 * 8);
+    G = G < 1 ? 1 : (G > 2048 ? 2048 : G);
+    dim3 grid((unsigned)G, (unsigned)n);
+    if (dtype == LINA_F32)
+        LINA_LAUNCH((rows_rearm_kernel<float>), grid, dim3(256), 0, stream, rows, n, B, seg_ptr, seg_row_bytes, n_seg,
+                    (const float*)y_start, (float*)x_out, (float*)x_out_packed, d, loop_ctl, txt_len, new_len);
+    else
+        LINA_LAUNCH((rows_rearm_kernel<bf16_t>), grid, dim3(256), 0, stream, rows, n, B, seg_ptr, seg_row_bytes, n_seg,
+                    (const bf16_t*)y_start, (bf16_t*)x_out, (bf16_t*)x_out_packed, d, loop_ctl, txt_len, new_len);
+    return check_launch("lina_rows_rearm");
+}
 
 extern "C" int lina_greedy_pick_embed(const void* logits, int64_t row_stride, const void* table, void* x_out,
                                       void* x_out_packed, int64_t* tok_log, int64_t* step, int* counter, int* loop_ctl, int B,

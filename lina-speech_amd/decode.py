@@ -20,6 +20,7 @@ The text side of the cross-attention is projected once (BlindCrossAttention.prep
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Optional
@@ -842,6 +843,7 @@ class DecodeEngine:
             part.packs = []
         self.parts, self.packs, self._state = [], [], None
         self._kk = self._vv = self._logits = self._att = self._y_in = self._txt_len = self._pe_rows = None
+        self._rearm_table = self._y_start = None
         self.model = None
 
     # names older callers / tests look at
@@ -1025,6 +1027,199 @@ class DecodeEngine:
         qs = L.tok_log[:n].permute(1, 2, 0).clone(memory_format=torch.contiguous_format)
         atts = L.att_log[:, :, :n].clone(memory_format=torch.contiguous_format) if L.att_log is not None else None
         return qs, atts, n
+
+    # ------------------------------------------------------------------ queue decoding: rows refilled between replays
+    def _require_queue(self):
+        if not self._ragged or len(self.parts) != 1 or not self._fused_pick or self.Q > 16:
+            raise NotImplementedError("queue decoding needs a ragged engine (x_lens) on one row range with the fused pick")
+
+    def _rearm_state(self):
+        """The segment table of K6g (built once per engine) and the start-token embedding [d]."""
+        if getattr(self, "_rearm_table", None) is None:
+            segs = [t for P in self.packs for t in (P.cq, P.ck, P.cv, P.S)]          # every block, the pos_net block included
+            try:
+                self._rearm_table = ops.RearmTable(segs, self.B)
+            except ValueError as e:
+                raise NotImplementedError(f"queue decoding: {e}")
+            y = self.model.rvq_embed.embed_sum(torch.ones(self.Q, 1, 1, dtype=torch.long, device=self.dev))
+            self._y_start = y.reshape(self.d).to(self.parts[0].x.dtype).contiguous()
+        return self._rearm_table, self._y_start
+
+    def rearm_rows(self, rows, x_enc_rows: torch.Tensor, lens):
+        """Start new utterances on ``rows`` (distinct row indices) of an armed loop, between two graph replays: their text side
+        (``x_enc_rows [m, Ttxt, d]`` from the text encoder under the ragged masks, ``lens`` its m text lengths, m >= n: the
+        first n are the rows' texts, the others padding that only keeps the shape of the projections fixed) is filed into
+        the engine's static buffers and one K6g launch zeroes their recurrent states and conv caches, writes the start-token
+        embedding into their input rows, clears their stop flags and sets their text lengths.  Legal only at a window
+        boundary -- ``(steps done - window origin) % window == 0``: the base state S is complete there and no history entry of
+        the old window is read again (K1w sums over s <= j) -- RuntimeError otherwise.  The other rows are not touched."""
+        self._require_queue()
+        if self._loop is None:
+            raise RuntimeError("rearm_rows: no armed loop (begin_greedy)")
+        if (self._n_done - self._origin_host) % self.window:
+            raise RuntimeError(f"rearm_rows: step {self._n_done} is not a window boundary (window {self.window}, origin "
+                               f"{self._origin_host})")
+        rows = [int(r) for r in rows]
+        n = len(rows)
+        if n < 1 or len(set(rows)) != n or min(rows) < 0 or max(rows) >= self.B:
+            raise ValueError(f"rearm_rows: rows must be distinct indices in [0, {self.B})")
+        if x_enc_rows.dim() != 3 or x_enc_rows.shape[0] < n or x_enc_rows.shape[1] != self.Tn:
+            raise ValueError(f"rearm_rows: x_enc_rows must be [m >= {n}, {self.Tn}, d]")
+        lens = text_lengths(lens, x_enc_rows.shape[0], self.Tn)
+        table, y_start = self._rearm_state()
+        kk, vv, pe = self.ca.prepare(x_enc_rows, lens=torch.tensor(lens))
+        lens = lens[:n]
+        idx = torch.tensor(rows, dtype=torch.long).to(self.dev)
+        self._kk.index_copy_(0, idx, kk.squeeze(1)[:n].to(self._kk.dtype))
+        self._vv.index_copy_(0, idx, vv.squeeze(1)[:n].to(self._vv.dtype))
+        if self.ca.per_row_table:                         # (a shared table does not depend on the lengths)
+            self._pe_rows.index_copy_(0, idx, pe.squeeze(1)[:n].to(self._pe_rows.dtype))
+        part = self.parts[0]
+        ops.rows_rearm(idx.to(torch.int32), table, y_start, part.x, x_packed=part.x_p if self._loop_packed else None,
+                       loop_ctl=self._loop.ctl, txt_len=self._txt_len,
+                       new_len=torch.tensor(lens, dtype=torch.int32).to(self.dev))
+
+    @torch.inference_mode()
+    def serve(self, caps, encode, finish, k: int = 1, temp: float = 1.0, first_greedy_quant: int = 0, seed: int = 0,
+              stop_check_every: int = 16, refill_rows: int = 32):
+        """The loop of ``generate()`` over a QUEUE of utterances (a generator): ``caps[i]`` is utterance i's step cap,
+        ``encode(ids, m) -> (x_enc_rows [m, Ttxt, d], lens [m])`` encodes the texts of the utterances ``ids`` (at most m; the
+        rows behind them are padding) when rows are free for them, ``finish(i, qs [Q,1,n], atts [1,2,n,Ttxt], txt_len)`` turns a
+        harvested utterance into what is yielded.  Texts are always encoded and projected m = min(B, ``refill_rows``) rows
+        at a time, however many rows are free: a GEMM library may pick another kernel, with another summation order, for
+        another row count, and an utterance's text side -- hence its attention weights, bit for bit -- must not depend on
+        how many rows happened to free up with it, i.e. on the queue's order.
+
+        Steps run in groups of ``every`` = ``stop_check_every`` rounded up to a multiple of max(GRAPH_STEPS, window); after
+        every group the control block's flags are copied to pinned memory behind the queued work, and the copy issued one
+        group earlier is looked at, together with the snapshot of which utterance each row carried then.  A row is finished
+        when its flag is set or its age has reached its cap: its token-log and attention-log rows are gathered from its start
+        position into fresh tensors (on the stream, before the re-arm), trimmed to its first stop step + 1 or its cap, and the
+        row is re-armed with the next queued text (``rearm_rows``) or left idle -- idle rows step on harmlessly.  Every group
+        boundary is a window boundary.  The logs are rings of ``cap`` steps (a multiple of 64 and of ``every``, >= max(caps) +
+        3 * every: a row is harvested at most 3 groups after its last useful step, and only its own lap could overwrite its
+        column): when the step counter reaches ``cap`` the host sets it and the window origin back to 0 -- the K1w phase is
+        unchanged -- and writes a new seed word derived from (seed, lap), since the draws hash (seed, step, row).
+        The captured graphs are those of ``generate()``; everything here happens between replays."""
+        self._require_queue()
+        caps = [int(c) for c in caps]
+        if any(c < 1 for c in caps):
+            raise ValueError("every step cap must be >= 1")
+        n_utts = len(caps)
+        if n_utts == 0:
+            return
+        B, N, R = self.B, self.GRAPH_STEPS, ops.LOOP_CTL_ROWS
+        unit = max(N, self.window)
+        every = (max(int(stop_check_every), 1) + unit - 1) // unit * unit
+        lcm = every * 64 // math.gcd(every, 64)
+        cap = (max(caps) + 3 * every + lcm - 1) // lcm * lcm
+        self.reset()
+        self.begin_greedy(cap, None, k=k, temp=temp, seed=seed, first_greedy_quant=first_greedy_quant, log_att=True)
+        L = self._loop
+        fused_seed = self.Q <= 16
+        cuda = self.dev.type == "cuda"
+        main = side = None
+        if cuda:
+            if getattr(self, "_serve_pin", None) is None or self._serve_pin[0].numel() != R + B:
+                self._serve_pin = [torch.empty(R + B, dtype=torch.int32).pin_memory() for _ in range(2)]
+                self._serve_ev = [torch.cuda.Event() for _ in range(2)]
+                self._serve_side = torch.cuda.Stream(device=self.dev)
+            main, side = torch.cuda.current_stream(self.dev), self._serve_side
+        self.ring_wraps, self.serve_every, self.serve_cap = 0, every, cap
+        chunk = max(1, min(B, int(refill_rows)))
+        utt, start, txt = [None] * B, [0] * B, [0] * B           # per row: the utterance it carries, its first step, its text length
+        nxt, live, abs_done = 0, 0, 0
+        pending = []                                              # harvested, not yet finished: (i, toks, att, txt_len, event)
+
+        def refill(rows):
+            nonlocal nxt, live
+            rows = rows[:n_utts - nxt]
+            if not rows:
+                return
+            for lo in range(0, len(rows), chunk):                 # one fixed shape for the encoder and the projections
+                grp = rows[lo:lo + chunk]
+                ids = list(range(nxt, nxt + len(grp)))
+                x_rows, lens = encode(ids, chunk)
+                lens = [int(v) for v in lens]
+                self.rearm_rows(grp, x_rows, lens)
+                for b, i, ln in zip(grp, ids, lens):
+                    utt[b], start[b], txt[b] = i, abs_done, ln
+                nxt += len(grp)
+                live += len(grp)
+
+        def harvest(b):
+            nonlocal live
+            i = utt[b]
+            n = min(caps[i], abs_done - start[b])
+            idx = (start[b] + torch.arange(n, device=self.dev)) % cap
+            toks = L.tok_log.index_select(0, idx)[:, :, b].t().contiguous()                       # [Q, n]
+            att = L.att_log[b].index_select(1, idx)                                               # [2, n, Ttxt]
+            ev = None
+            if cuda:
+                ev = torch.cuda.Event()
+                ev.record(main)
+            pending.append((i, toks, att, txt[b], ev))
+            utt[b] = None
+            live -= 1
+
+        def finish_pending():
+            """Trim and finish what was harvested one group ago (its gathers have completed: no wait behind the queued steps;
+            on a ROCm device the read-backs run on a side stream for the same reason)."""
+            out = []
+            todo, pending[:] = list(pending), []
+            for i, toks, att, ln, ev in todo:
+                if cuda:
+                    side.wait_event(ev)
+                    toks.record_stream(side)
+                    att.record_stream(side)
+                with (torch.cuda.stream(side) if cuda else contextlib.nullcontext()):
+                    stops = (toks == 2).all(dim=0)
+                    hit = torch.nonzero(stops).flatten()
+                    n = int(hit[0]) + 1 if hit.numel() else toks.shape[1]
+                    out.append(finish(i, toks[:, None, :n], att[None, :, :n], ln))
+            return out
+
+        refill(list(range(min(B, n_utts))))
+        prev = None                                               # (slot or host copy, snapshot of utt) of the last copy issued
+        while live > 0 or nxt < n_utts:
+            self.greedy_steps(every)
+            abs_done += every
+            if self._n_done >= cap:                               # the ring's lap: a window boundary
+                self._t_idx.zero_()
+                self._origin.zero_()
+                self._n_done = self._origin_host = 0
+                self.ring_wraps += 1
+                word = (int(seed) + 0x9E3779B97F4A7C15 * self.ring_wraps) & (2 ** 63 - 1)
+                L.ctl[2:4].copy_(ops.new_loop_ctl(0, "cpu", word if fused_seed else 0)[2:4])
+            if prev is not None:
+                flags, carried = prev
+                if cuda:
+                    self._serve_ev[flags].synchronize()
+                    flags = self._serve_pin[flags]
+                for res in finish_pending():                      # (harvested before that copy was issued)
+                    yield res
+                free = []
+                for b in range(B):
+                    i = utt[b]
+                    if i is None:
+                        free.append(b)
+                    elif (carried[b] == i and int(flags[R + b])) or abs_done - start[b] >= caps[i]:
+                        harvest(b)
+                        free.append(b)
+                refill(free)
+            if cuda:
+                slot = 1 if (prev is not None and prev[0] == 0) else 0
+                self._serve_pin[slot].copy_(L.ctl[:R + B], non_blocking=True)
+                self._serve_ev[slot].record()
+                prev = (slot, list(utt))
+            else:
+                prev = (L.ctl[:R + B].clone(), list(utt))
+        if cuda:
+            main.synchronize()
+        for res in finish_pending():
+            yield res
+        if cuda:
+            main.wait_stream(side)
 
     def poll_stop(self, slot: int):
         """Queue a copy of the control block's first two words to pinned slot ``slot`` behind the work enqueued so far."""

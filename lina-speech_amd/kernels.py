@@ -372,6 +372,59 @@ def pick_embed_forced(logits, table, x_out, tok_log, step, counter, force_tok, f
                                          force_tok.shape[0], _dt(table), be.stream(table)))
 
 
+class RearmTable:
+    """The state segments ``rows_rearm`` zeroes, built once per engine: ``tensors`` are the [B, ...] state tensors (conv caches
+    and recurrent states, fp32 or bf16, contiguous rows); segment s is ``tensors[s]``, its row b ``ptr[s] + b * row_bytes[s]``.
+    Holds the device tables (int64 words: the pointer bits / the row sizes), the host copy of the sizes and the tensors
+    themselves (the table is addresses: they must stay alive)."""
+
+    def __init__(self, tensors, B: int):
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError("RearmTable: no state tensors")
+        sizes = []
+        for t in tensors:
+            if t.dim() < 1 or t.shape[0] != B or not t[0].is_contiguous():
+                raise ValueError(f"RearmTable: every segment is a [B = {B}, ...] tensor with contiguous rows")
+            rb = (t.stride(0) if B > 1 else t[0].numel()) * t.element_size()
+            if rb <= 0 or rb % 16 or t.data_ptr() % 16:
+                raise ValueError(f"RearmTable: a row of {rb} bytes -- rows must be 16-byte aligned multiples of 16 bytes")
+            sizes.append(rb)
+        dev = tensors[0].device
+        self.tensors, self.B, self.n_seg = tensors, B, len(tensors)
+        self.row_bytes_host = torch.tensor(sizes, dtype=torch.int64)
+        self.row_bytes = self.row_bytes_host.to(dev)
+        self.ptr = torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).to(dev)
+
+
+def rows_rearm(rows, table: RearmTable, y_start, x_out, x_packed=None, loop_ctl=None, txt_len=None, new_len=None):
+    """K6g (lina_rows_rearm): re-arm the listed batch rows between two replays of the decode loop -- ``rows`` int32 [n]
+    (distinct, each in [0, B)): their rows of every segment of ``table`` zeroed, ``x_out[b] = y_start`` ([d]; ``x_packed``: the
+    fragment-major copy too), their stop flags in ``loop_ctl`` cleared (word [0] reduced by the number that were set, word [1]
+    = -1) and ``txt_len[rows[i]] = new_len[i]`` (int32 [B] / [n]).  Rows not listed are untouched.  One launch."""
+    be = _backend._BACKEND
+    be.require(rows, table.ptr, table.row_bytes, y_start, x_out, x_packed, loop_ctl, txt_len, new_len)
+    B, d = x_out.shape
+    n = rows.numel()
+    if rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous() or not 1 <= n <= B:
+        raise ValueError("rows must be a contiguous int32 [n] tensor, 1 <= n <= B")
+    if table.B != B:
+        raise ValueError(f"the segment table was built for {table.B} rows, x_out has {B}")
+    if not x_out.is_contiguous() or y_start.dtype != x_out.dtype or y_start.numel() != d or not y_start.is_contiguous():
+        raise ValueError("x_out must be a contiguous [B, d] tensor and y_start a contiguous [d] tensor of its dtype")
+    if x_packed is not None and (x_packed.numel() < packed_numel(B, d) or x_packed.dtype != x_out.dtype):
+        raise ValueError("packed x buffer is too small")
+    if (txt_len is None) != (new_len is None):
+        raise ValueError("txt_len and new_len go together")
+    if txt_len is not None and (txt_len.dtype != torch.int32 or tuple(txt_len.shape) != (B,) or not txt_len.is_contiguous()
+                                or new_len.dtype != torch.int32 or tuple(new_len.shape) != (n,) or not new_len.is_contiguous()):
+        raise ValueError("txt_len must be a contiguous int32 [B] tensor and new_len a contiguous int32 [n] tensor")
+    _check(be.lib.lina_rows_rearm(_ptr(rows), n, B, _ptr(table.ptr), _ptr(table.row_bytes), _ptr(table.row_bytes_host),
+                                  table.n_seg, _ptr(y_start), _ptr(x_out), _ptr(x_packed), d,
+                                  _loop_ctl_ptr(be, loop_ctl, B), _ptr(txt_len), _ptr(new_len), _dt(x_out),
+                                  be.stream(x_out)))
+
+
 # --------------------------------------------------------------------------- decode-step fusions
 def topk_sample_rows(logits, k: int, temp: float = 1.0, u: Optional[torch.Tensor] = None, seed: int = 0,
                      step: Optional[torch.Tensor] = None, out=None):

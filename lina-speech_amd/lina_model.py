@@ -326,6 +326,91 @@ class LinaModel(nn.Module):
         qs = torch.stack(qs, dim=2).squeeze(-1)                                  # [Q,B,n]
         return self._finish_generate(qs, atts, torch.cat(stop_tokens, dim=1), B, device, lens)
 
+    # ------------------------------------------------------------------ queue decode: finished rows take the next text
+    def generate_stream(self, texts, batch_size: int, max_seqlen=1000, k: int = 100, first_greedy_quant: int = 1,
+                        temp: float = 1.0, seed: Optional[int] = None, stop_check_every: int = 16,
+                        state_dtype: Optional[torch.dtype] = None, device: str = "cpu", max_text_len: Optional[int] = None,
+                        prompt=None, init_state=None):
+        """Decode a QUEUE of N texts on ``batch_size`` rows (ours; the device-side loop only): a row whose utterance has
+        stopped -- or reached its step cap -- is re-armed with the next queued text between two graph replays while the other
+        rows go on (decode.DecodeEngine.serve, K6g), instead of stepping on until the slowest row of its batch has stopped.
+        A generator yielding ``(i, codes, att)`` as utterances finish (not in queue order).
+
+        ``texts``: N 1-D LongTensors; ``max_seqlen``: an int or N ints, the step cap of each utterance.  ``(codes, att)`` of
+        utterance i is ``cuts[0]`` of ``generate_batch(texts[i], batch_size=1, max_seqlen=cap_i, ...)``: the reference's
+        post-processing (``_finish_generate``) of the row's own steps, trimmed to its first stop step + 1 or its cap.  Greedy
+        results (k = 1 or first_greedy_quant = 0) do not depend on ``batch_size``, on the queue order or on
+        ``stop_check_every``.  SAMPLED results are reproducible for a fixed (seed, batch_size, order, stop_check_every) but are
+        NOT those of the alone run: the draws hash (seed, step of the loop, row), and an utterance's row and start step depend
+        on the queue.  Utterances start on window boundaries at the loop's checks: a row idles up to 2 * ``every`` steps
+        between two utterances (``every`` = stop_check_every rounded up to a multiple of max(8, window)).
+        The texts are encoded in refill batches of one fixed row count (min(batch_size, 32), padded) under the ragged masks,
+        so that an utterance's result, bit for bit, does not depend on which others were refilled with it; the engine is the
+        cached ragged engine of (batch_size, ``max_text_len`` or the longest text).  With N < batch_size the spare rows idle
+        from the start.
+        ``prompt``, ``init_state``, a speaker encoder and an architecture the engine does not cover raise
+        NotImplementedError: there is no fallback to the module path."""
+        if prompt is not None or init_state is not None:
+            raise NotImplementedError("generate_queue: codec prompts and start states for refilled rows are not built")
+        if self.spk_encoder is not None:
+            raise NotImplementedError("generate_queue: no speaker encoder")
+        texts = list(texts)
+        n_utts = len(texts)
+        if any((not isinstance(t, Tensor)) or t.dim() != 1 or t.shape[0] < 1 for t in texts):
+            raise ValueError("texts: a list of non-empty 1-D LongTensors")
+        caps = [int(max_seqlen)] * n_utts if isinstance(max_seqlen, int) else [int(c) for c in max_seqlen]
+        if len(caps) != n_utts or any(c < 1 for c in caps):
+            raise ValueError(f"max_seqlen: an int or one step cap >= 1 per text ({n_utts})")
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        lens_all = [int(t.shape[0]) for t in texts]
+        Tn = int(max_text_len) if max_text_len else max(lens_all, default=1)
+        if lens_all and max(lens_all) > Tn:
+            raise ValueError(f"a text is longer than max_text_len = {Tn}")
+        return self._queue_gen(texts, lens_all, caps, batch_size, Tn, k, first_greedy_quant, temp, seed, stop_check_every,
+                               state_dtype, device)
+
+    @torch.inference_mode()
+    def _queue_gen(self, texts, lens_all, caps, B, Tn, k, first_greedy_quant, temp, seed, stop_check_every, state_dtype,
+                   device):
+        if not texts:
+            return
+        w = self.logits_head.weight
+        idle = torch.zeros(B, Tn, self.txt_embed.weight.shape[1], dtype=w.dtype, device=device)
+        eng = self._decode_engine(idle, B, None, 1, state_dtype, x_lens=torch.ones(B, dtype=torch.long))
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)))
+
+        def encode(ids, m):                                  # a refill batch through the text encoder, ragged masks: always
+            x = torch.zeros(m, Tn, dtype=torch.long, device=device)      # m rows (padding: one-token texts), so that an
+            for r, i in enumerate(ids):                                  # utterance's text side does not depend on how many
+                x[r, :lens_all[i]] = texts[i].to(device)                 # rows were free with it
+            lens = [lens_all[i] for i in ids] + [1] * (m - len(ids))
+            ln = torch.tensor(lens, device=device)
+            live = torch.arange(Tn, device=device)[None, :] < ln[:, None]
+            return self.txt_encoder(self.txt_embed(x), mask=live[:, None, :] & live[:, :, None]), lens
+
+        def finish(i, qs, atts, txt_len):
+            cuts = self._finish_generate(qs, atts, (qs == 2).all(dim=0), 1, device, torch.tensor([txt_len]))[3]
+            return i, cuts[0][0], cuts[0][1]
+
+        yield from eng.serve(caps, encode, finish, k=k, temp=temp, first_greedy_quant=first_greedy_quant, seed=seed,
+                             stop_check_every=stop_check_every)
+
+    def generate_queue(self, texts, batch_size: int, max_seqlen=1000, k: int = 100, first_greedy_quant: int = 1,
+                       temp: float = 1.0, seed: Optional[int] = None, stop_check_every: int = 16,
+                       state_dtype: Optional[torch.dtype] = None, device: str = "cpu", max_text_len: Optional[int] = None,
+                       prompt=None, init_state=None):
+        """``generate_stream`` collected: N pairs ``(codes, att)`` in queue order ([] for an empty queue)."""
+        texts = list(texts)
+        out = [None] * len(texts)
+        for i, codes, att in self.generate_stream(texts, batch_size, max_seqlen=max_seqlen, k=k,
+                                                  first_greedy_quant=first_greedy_quant, temp=temp, seed=seed,
+                                                  stop_check_every=stop_check_every, state_dtype=state_dtype, device=device,
+                                                  max_text_len=max_text_len, prompt=prompt, init_state=init_state):
+            out[i] = (codes, att)
+        return out
+
     @staticmethod
     def _ragged_text(x, B: int, x_lens):
         """generate_batch's text argument -> (x, lengths [B] LongTensor or None).  A list of B 1-D texts is right-padded with
