@@ -22,6 +22,14 @@ __device__ __forceinline__ float wave_sum(float v) {
     v += shfl_xor(v, 8); v += shfl_xor(v, 16); v += shfl_xor(v, 32);
     return v;
 }
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const unsigned lo = (unsigned)shfl_xor_i((int)(unsigned)v, m), hi = (unsigned)shfl_xor_i((int)(unsigned)(v >> 32), m);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
 
 // TX: residual-stream dtype (x, xsum, dx);  TR: dtype of the added branch r (and of its gradient);  TY: output dtype
 // All loads of a row are UNCONDITIONAL on clamped element offsets and issued before anything uses them (a load under a
@@ -396,8 +404,13 @@ __global__ __launch_bounds__(64 * kSumWaves) void sum_partials_kernel(const floa
 // (rows of an odd width start on any 2-byte boundary: the groups are laid on the 8-byte grid below the row start and the
 // elements outside the row masked), then max, sum of exponentials and the target's logit come from registers.  The backward
 // rebuilds softmax from the row and the saved log-sum-exp: d logits = (softmax - onehot) * scale for rows that count, 0 for
-// ignored rows.  fp32 arithmetic from the stored dtype, as autocast's fp32 log_softmax -- without its fp32 copy of the logits
-// (537 MB at config 5), the two casts and the separate log_softmax / nll kernels and their backwards.
+// ignored rows.  The groups sit on the aligned grid, so WHICH lane and register holds a column depends on where the row starts
+// (row * ld mod 4: with an odd width, on the row's index): a floating-point sum of the exponentials in lane / register order
+// would give a row other bits in another row slot.  The exponentials (in (0, 1], the largest is 1) are therefore summed as
+// integers in units of 2^-40 -- the same sum in any order, at most V * 2^-40 < 1e-8 below the exact one (sum >= 1), well
+// inside fp32 rounding.  A NaN / +inf logit still gives the row a NaN log-sum-exp (cost: profiles/k14_fixed_point_sum.txt).
+// fp32 arithmetic from the stored dtype, as autocast's fp32 log_softmax -- without its fp32 copy of the logits (537 MB at
+// config 5), the two casts and the separate log_softmax / nll kernels and their backwards.
 __device__ __forceinline__ float4 pack4(const float (&e)[4]) { return make_float4(e[0], e[1], e[2], e[3]); }
 __device__ __forceinline__ uint2 pack4(const bf16_t (&e)[4]) {
     return make_uint2((uint32_t)e[0] | ((uint32_t)e[1] << 16), (uint32_t)e[2] | ((uint32_t)e[3] << 16));
@@ -471,7 +484,8 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const T* __restrict_
                 for (int c = 0; c < 4; ++c) m = fmaxf(m, in[c] ? v[c] : -INFINITY);
             }
             m = wave_max(m);
-            float se = 0.0f, xt = 0.0f;
+            unsigned long long se_fix = 0;                            // sum of exp(v - m) in units of 2^-40: any order, same sum
+            float xt = 0.0f, bad = 0.0f;                              // (xt: one nonzero term; bad: 0 or NaN)
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 float v[4]; bool in[4];
@@ -479,13 +493,16 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const T* __restrict_
                 const int p = 4 * (g * 64 + lane) - r.lo;             // column of element 0 of this group
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    se += in[c] ? __expf(v[c] - m) : 0.0f;
+                    const float e = __expf(v[c] - m);
+                    const bool ok = e <= 2.0f;                        // false: a NaN (NaN or +inf logit); e <= 1 up to rounding
+                    se_fix += (in[c] && ok) ? (unsigned long long)(e * 0x1p40f) : 0ull;
+                    bad = (in[c] && !ok) ? NAN : bad;
                     xt += (in[c] && p + c == tg) ? v[c] : 0.0f;
                 }
             }
-            se = wave_sum(se);
+            const float se = (float)wave_sum_u64(se_fix) * 0x1p-40f;
             xt = wave_sum(xt);
-            const float l = m + __logf(se);
+            const float l = m + __logf(se) + wave_sum(bad);
             if (lane == 0) {
                 lse[row] = l;
                 loss_row[row] = counts ? l - xt : 0.0f;
