@@ -642,6 +642,36 @@ int lina_dwconv7_ln(const void* x, const void* w, const void* bias, const void* 
 int lina_istft_ola(const float* frames, const float* window, float* y, int B, int T, int win, int hop,
                    lina_stream_t stream);
 
+/* Ragged vocoder batches: B right-padded rows of different lengths.  lens: int32 [B] on the device, row b's number of live
+ * positions L_b (a value outside [0, L] is clamped to that range); L (T) stays the row stride.  Row b of each of the three
+ * launches below is, bit for bit, what the same arithmetic gives for x[b, ..., :L_b] alone as a batch of one: positions past
+ * L_b are never read, and they are WRITTEN as exact zeros (the zero padding a "same" convolution that follows would supply
+ * for the row alone). */
+
+/* K8r -- K8 with a length per row: taps at t' < 0 or t' >= L_b read as zero; rows t < L_b get K8's result (the same
+ * per-row arithmetic in the same order), rows t >= L_b zeros.  A wave whose 8-row run lies past L_b only writes zeros.
+ * Shapes, dtypes, C <= 1024 and scale_sb as K8. */
+int lina_dwconv7_ln_ragged(const void* x, const void* w, const void* bias, const void* scale, const void* shift,
+                           void* y, const int32_t* lens, int B, int L, int C, int64_t scale_sb, float eps, int dtype,
+                           lina_stream_t stream);
+
+/* K9r -- K9 with T_b = lens[b] frames per row (win - hop even):
+ *   frames: fp32 [B, T, win];  y: fp32 [B, T*hop].  Sample n < T_b*hop gathers frames t <= T_b - 1 only, for the sum and for
+ *   the envelope (K9 on frames[b, :T_b] alone); samples n >= T_b*hop are zero. */
+int lina_istft_ola_ragged(const float* frames, const float* window, float* y, const int32_t* lens, int B, int T,
+                          int win, int hop, lina_stream_t stream);
+
+/* K10g -- GroupNorm over a row's own positions, channels-first (the layout of backbone.pos_net):
+ *   x, y: [B, C, L] contiguous (model dtype);  weight / bias: [C] (model dtype) or NULL;  G groups, C % G == 0;
+ *   lens: int32 [B] or NULL (every row has L positions);  act: LINA_ACT_NONE or LINA_ACT_SILU.
+ *   y[b, c, t] = act((x - mean) * rsqrt(var + eps) * weight[c] + bias[c]) for t < L_b, 0 for t >= L_b, with mean and the
+ *   biased variance (centred sum of squares) in fp32 over the (C/G) * L_b live elements of (b, group of c).
+ * One workgroup per (b, group); the order of the additions depends on the logical index (c - c0) * L_b + t alone, not on L,
+ * b or the strides; the cross-wave sum goes through LDS in a fixed order (no atomics). */
+enum { LINA_ACT_NONE = 0, LINA_ACT_SILU = 1 };
+int lina_group_norm_ragged(const void* x, const void* weight, const void* bias, void* y, const int32_t* lens, int B,
+                           int C, int L, int G, float eps, int act, int dtype, lina_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,9 @@ PROTOTYPES = {
     "lina_topk_sample_rows": (C.c_int, [_p, _p, _i64, _i, _i64, _i, _f, _p, C.c_uint64, _p, _i, _p]),
     "lina_dwconv7_ln": (C.c_int, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i64, _f, _i, _p]),
     "lina_istft_ola": (C.c_int, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "lina_dwconv7_ln_ragged": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i64, _f, _i, _p]),
+    "lina_istft_ola_ragged": (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "lina_group_norm_ragged": (C.c_int, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _i, _p]),
     "lina_gla_decode_prologue": (C.c_int, [_p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                            _i, _i, _i, _i, _i, _f, _f, _i, _p]),
     "lina_swiglu": (C.c_int, [_p, _p, _i64, _i, _i64, _i64, _i, _p]),

@@ -947,13 +947,8 @@ def weighted_rows_add(attc, vv, x, x_packed=None):
 
 
 # --------------------------------------------------------------------------- codes -> waveform (f-3)
-def dwconv7_ln(x, weight, bias=None, scale=None, shift=None, eps: float = 1e-6):
-    """K8: depthwise conv (k = 7, 'same') + LayerNorm over channels, channels-last ``x [B,L,C]``
-    (ConvNeXtBlock.dwconv + norm, reference 3rdparty/decoder/modules.py:44-50).  ``weight`` [C,1,7]|[C,7];
-    ``scale`` / ``shift``: [C] (LayerNorm affine) or [B,C] (AdaLayerNorm rows) or None."""
-    _no_grad(x, weight, bias, scale, shift)
-    be = _backend._BACKEND
-    be.require(x, weight, bias, scale, shift)
+def _dwconv7_args(x, weight, bias, scale, shift):
+    """Operands of K8 / K8r as the launch takes them: (x, w [C,7], bias, scale, shift, scale_sb), all in x's dtype."""
     B, L, Cc = x.shape
     x = x.contiguous()
     w = weight.reshape(Cc, 7).to(x.dtype).contiguous()
@@ -970,9 +965,44 @@ def dwconv7_ln(x, weight, bias=None, scale=None, shift=None, eps: float = 1e-6):
             raise ValueError("scale and shift must have the same shape")
         if scale is None:
             sb = Cc if shift.dim() == 2 and shift.shape[0] == B and B > 1 else 0
+    return x, w, b, scale, shift, sb
+
+
+def dwconv7_ln(x, weight, bias=None, scale=None, shift=None, eps: float = 1e-6):
+    """K8: depthwise conv (k = 7, 'same') + LayerNorm over channels, channels-last ``x [B,L,C]``
+    (ConvNeXtBlock.dwconv + norm, reference 3rdparty/decoder/modules.py:44-50).  ``weight`` [C,1,7]|[C,7];
+    ``scale`` / ``shift``: [C] (LayerNorm affine) or [B,C] (AdaLayerNorm rows) or None."""
+    _no_grad(x, weight, bias, scale, shift)
+    be = _backend._BACKEND
+    be.require(x, weight, bias, scale, shift)
+    B, L, Cc = x.shape
+    x, w, b, scale, shift, sb = _dwconv7_args(x, weight, bias, scale, shift)
     y = torch.empty_like(x)
     _check(be.lib.lina_dwconv7_ln(_ptr(x), _ptr(w), _ptr(b), _ptr(scale), _ptr(shift), _ptr(y), B, L, Cc, sb, float(eps),
                                   _dt(x), be.stream(x)))
+    return y
+
+
+def _row_lens_arg(lens, B: int, name: str = "lens"):
+    """The device lengths of the ragged vocoder launches: int32 [B] (values within the padded length are the caller's
+    promise -- a device tensor is not read back here; the kernels clamp)."""
+    if lens is None or lens.dtype != torch.int32 or lens.dim() != 1 or lens.shape[0] != B or not lens.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous int32 [B] tensor of row lengths")
+
+
+def dwconv7_ln_ragged(x, weight, bias=None, scale=None, shift=None, eps: float = 1e-6, *, lens):
+    """K8r: ``dwconv7_ln`` for right-padded rows, ``lens`` int32 [B] on x's device: row b's first ``lens[b]`` time steps are
+    ``dwconv7_ln(x[b:b+1, :lens[b]])`` bit for bit (taps past the row's end read as zero, x there is not read), the rest of
+    the row is written as zeros."""
+    _no_grad(x, weight, bias, scale, shift)
+    be = _backend._BACKEND
+    be.require(x, weight, bias, scale, shift, lens)
+    B, L, Cc = x.shape
+    _row_lens_arg(lens, B)
+    x, w, b, scale, shift, sb = _dwconv7_args(x, weight, bias, scale, shift)
+    y = torch.empty_like(x)
+    _check(be.lib.lina_dwconv7_ln_ragged(_ptr(x), _ptr(w), _ptr(b), _ptr(scale), _ptr(shift), _ptr(y), _ptr(lens), B, L, Cc,
+                                         sb, float(eps), _dt(x), be.stream(x)))
     return y
 
 
@@ -987,4 +1017,50 @@ def istft_ola(frames, window, hop: int):
     pad = (win - hop) // 2
     y = torch.empty(B, (T - 1) * hop + win - 2 * pad, dtype=torch.float32, device=frames.device)
     _check(be.lib.lina_istft_ola(_ptr(frames), _ptr(window), _ptr(y), B, T, win, int(hop), be.stream(frames)))
+    return y
+
+
+def istft_ola_ragged(frames, window, hop: int, lens):
+    """K9r: ``istft_ola`` for right-padded rows, ``lens`` int32 [B] frames per row: fp32 [B, T*hop] whose row b starts with
+    ``istft_ola(frames[b:b+1, :lens[b]])`` bit for bit (frames past the row's end are not read) and is zero from sample
+    ``lens[b] * hop`` on (win - hop even)."""
+    be = _backend._BACKEND
+    be.require(frames, window, lens)
+    B, T, win = frames.shape
+    _row_lens_arg(lens, B)
+    if (win - int(hop)) % 2:
+        raise ValueError("istft_ola_ragged: win - hop must be even")
+    frames = frames.float().contiguous()
+    window = window.float().contiguous()
+    y = torch.empty(B, T * int(hop), dtype=torch.float32, device=frames.device)
+    _check(be.lib.lina_istft_ola_ragged(_ptr(frames), _ptr(window), _ptr(y), _ptr(lens), B, T, win, int(hop),
+                                        be.stream(frames)))
+    return y
+
+
+_GN_ACTS = {None: 0, "none": 0, "silu": 1}          # LINA_ACT_*
+
+
+def group_norm_ragged(x, num_groups: int, weight=None, bias=None, eps: float = 1e-5, act=None, lens=None):
+    """K10g: GroupNorm (+ optional SiLU) of channels-first ``x [B,C,L]`` over each row's own ``lens[b]`` positions (``lens``
+    int32 [B] on x's device; None: all L): statistics in fp32 over the (C/G) * lens[b] live elements, zeros written for
+    t >= lens[b].  Row b is bit-equal to the same call on ``x[b:b+1, :, :lens[b]]`` alone."""
+    _no_grad(x, weight, bias)
+    be = _backend._BACKEND
+    be.require(x, weight, bias, lens)
+    if x.dim() != 3:
+        raise ValueError("group_norm_ragged: x must be [B, C, L]")
+    B, Cc, L = x.shape
+    if act not in _GN_ACTS:
+        raise ValueError("group_norm_ragged: act must be None, 'none' or 'silu'")
+    if num_groups < 1 or Cc % num_groups:
+        raise ValueError(f"group_norm_ragged: C = {Cc} is not divisible by {num_groups} groups")
+    if lens is not None:
+        _row_lens_arg(lens, B)
+    x = x.contiguous()
+    w = None if weight is None else weight.to(x.dtype).contiguous()
+    b = None if bias is None else bias.to(x.dtype).contiguous()
+    y = torch.empty_like(x)
+    _check(be.lib.lina_group_norm_ragged(_ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(lens), B, Cc, L, int(num_groups),
+                                         float(eps), _GN_ACTS[act], _dt(x), be.stream(x)))
     return y

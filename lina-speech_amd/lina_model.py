@@ -411,6 +411,44 @@ class LinaModel(nn.Module):
             out[i] = (codes, att)
         return out
 
+    @torch.inference_mode()
+    def synthesize(self, texts, vocoder, batch_size: int, *, vocoder_batch: int = 32, bandwidth_id=None,
+                   **generate_queue_kwargs):
+        """Texts in, waveforms out (ours): ``generate_stream`` feeding the ragged vocoder.  N 1-D waveforms in queue order,
+        utterance i's being ``vocoder(codes_i, bandwidth_id)`` of its own codes alone (``codes_i`` as ``generate_queue``
+        returns them, ``len(codes_i) * hop`` samples).  Finished utterances are collected, sorted by length and vocoded
+        ``vocoder_batch`` at a time with their lengths (``WavTokenizerDecoder.forward(..., lens=...)``), which bounds the
+        padding of a group by the spread of neighbouring lengths.  An utterance whose cut holds no code gives an empty
+        waveform and is not sent to the vocoder.  ``vocoder.n_codes`` must cover the model's ``n_codebook``; the restrictions
+        of ``generate_stream`` apply (no prompt, no start state, no speaker encoder)."""
+        if vocoder_batch < 1:
+            raise ValueError("vocoder_batch must be >= 1")
+        if vocoder.n_codes < self.n_codebook:
+            raise ValueError(f"the vocoder knows {vocoder.n_codes} codes, the model emits {self.n_codebook}")
+        texts = list(texts)
+        codes = [None] * len(texts)
+        for i, c, _ in self.generate_stream(texts, batch_size, **generate_queue_kwargs):
+            codes[i] = c
+        return self.vocode(codes, vocoder, vocoder_batch=vocoder_batch, bandwidth_id=bandwidth_id)
+
+    @staticmethod
+    @torch.inference_mode()
+    def vocode(codes, vocoder, *, vocoder_batch: int = 32, bandwidth_id=None):
+        """The second half of ``synthesize``: N code cuts ``[Q, 1, n_i]`` (or ``[Q, n_i]``; as ``generate_queue`` returns them)
+        -> N 1-D waveforms of ``n_i * hop`` samples in the same order, through the ragged vocoder in groups of
+        ``vocoder_batch`` utterances sorted by length; an empty cut gives an empty waveform without a vocoder call."""
+        if vocoder_batch < 1:
+            raise ValueError("vocoder_batch must be >= 1")
+        w = vocoder.head.istft.window
+        codes = [c[:, 0] if c.dim() == 3 else c for c in codes]            # [Q, n_i]
+        out = [torch.zeros(0, dtype=torch.float32, device=w.device) for _ in codes]
+        order = sorted((i for i, c in enumerate(codes) if c.shape[-1] > 0), key=lambda i: codes[i].shape[-1])
+        for lo in range(0, len(order), vocoder_batch):
+            ids = order[lo:lo + vocoder_batch]
+            for i, wav in zip(ids, vocoder([codes[i].to(w.device) for i in ids], bandwidth_id)):
+                out[i] = wav
+        return out
+
     @staticmethod
     def _ragged_text(x, B: int, x_lens):
         """generate_batch's text argument -> (x, lengths [B] LongTensor or None).  A list of B 1-D texts is right-padded with

@@ -30,7 +30,7 @@ from .kernels import (
     gla_decode_window, gla_decode_window_flush, wave_sum_selftest, cross_att_step1, cross_att_step2, cross_scores,
     cross_scores_softmax, softmax_weighted_rows_add, pe_softmax_weighted_rows_add, softmax_pe_rows, softmax_rows, weighted_rows_add, dwconv7_ln,
     cross_scores_ragged, softmax_pe_rows_ragged, pe_softmax_weighted_rows_add_ragged,
-    istft_ola)
+    istft_ola, dwconv7_ln_ragged, istft_ola_ragged, group_norm_ragged)
 from .autograd import (
     _GLAFunction, _needs_grad, _gla, fused_recurrent_gla, naive_recurrent_gla, chunk_gla, fused_chunk_gla,
     chunk_simple_gla, GradSlab, _slab_part, _SplitSlabFunction, split_slab, _ShortConvFunction, short_conv, _ShortConv3Function, short_conv3,
